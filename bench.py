@@ -10,11 +10,17 @@ Weak scaling: per-GPU batch fixed at 32, N ranks, data parallel over RCCL.
 
 Timed region: exactly K full optimizer steps (on-device batch draw + forward +
 loss + backward + bucketed all-reduce + clip + AdamW + LR schedule), bracketed
-by barrier + synchronize on both sides; max over ranks.  Also reports (extra
-keys, rank 0, outside the timed region) the DDIM k=20 / N=64 sampler
-throughput of the hipGraph-captured sampling loop.
+by barrier + synchronize on both sides; max over ranks.  A plain run does only
+that: set-up, warm-up, the timed steps, the result line.  ``--full`` (1 GPU) adds,
+as extra keys measured outside the timed region, the other training
+configurations, the same-node vendor comparators and the DDIM k=20 / N=64
+sampler and img2img throughputs with their eager / vendor comparators.
+``--dump-outputs DIR`` writes what the last timed step left (its loss and the
+updated parameters) as ``DIR/<name>.npy``; the inputs are seeded, so two builds
+run with the same arguments can be compared output for output.
 
-    python bench.py                       # 1 GPU
+    python bench.py                       # 1 GPU, headline only
+    python bench.py --full                # + every extra key
     python bench.py --gpus N              # N ranks, spawned here (one process per GPU)
     torchrun --nproc-per-node N bench.py --gpus N --steps K --warmup W
 
@@ -59,7 +65,14 @@ def parse_args(argv=None):
                          "rest of the --warmup steps replay the captured K-step graph, so the timed steps start "
                          "on a graph that has run and a device that is busy (profiles/first_replay_r6.txt)")
     ap.add_argument("--bucket-blocks", type=int, default=2)
-    ap.add_argument("--no-sampler", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="1 GPU: after the headline also measure the extra keys (Gaussian-DDIM / vit_small_200 / "
+                         "oxford_flower training, vendor comparators, DDIM sampler and img2img with their eager "
+                         "baselines); each group can be left out with its --no-* switch")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write their result (last step's loss, updated parameters) as "
+                         "DIR/<name>.npy (float32; a fixed seeded sample of an array above 4M elements)")
+    ap.add_argument("--no-sampler", action="store_true", help="--full: skip the sampler / img2img keys")
     ap.add_argument("--force-dist", action="store_true",
                     help="init the RCCL process group and run segmented graphs + collectives even with 1 rank")
     ap.add_argument("--segmented-comm", action="store_true",
@@ -84,14 +97,14 @@ def parse_args(argv=None):
                     help="training task of the timed steps: cold pixelation pairs (the reference's measured "
                          "run) or Gaussian DDIM (diffusion_loader.DiffusionDataset: q_sample, t in 0..1999)")
     ap.add_argument("--no-gaussian", action="store_true",
-                    help="1 GPU: skip the extra Gaussian-DDIM training throughput key")
+                    help="--full: skip the extra Gaussian-DDIM training throughput key")
     ap.add_argument("--no-hires", action="store_true",
-                    help="1 GPU: skip the extra vit_small_200 (200x200, BASELINE.json config 4) and "
+                    help="--full: skip the extra vit_small_200 (200x200, BASELINE.json config 4) and "
                          "oxford_flower training keys")
     ap.add_argument("--no-eager-baseline", action="store_true",
-                    help="skip timing the plain eager PyTorch sampler (BASELINE.md's sampling comparator)")
+                    help="--full: skip timing the plain eager PyTorch sampler (BASELINE.md's sampling comparator)")
     ap.add_argument("--no-vendor", action="store_true",
-                    help="1 GPU: skip the same-node vendor comparators (stock PyTorch-ROCm ops: hipBLASLt, SDPA, "
+                    help="--full: skip the same-node vendor comparators (stock PyTorch-ROCm ops: hipBLASLt, SDPA, "
                          "fused AdamW; training step and DDIM sampler each captured whole in one graph)")
     return ap.parse_args(argv)
 
@@ -223,6 +236,23 @@ def _time_train(args, name, dataset, dev, lr, seed, prefix, pool=None):
             f"{prefix}_final_loss": round(loss, 5)}
 
 
+DUMP_MAX_ELEMS = 4 << 20  # per array: 16 MB of float32, far under the 64 MB allowed in all
+
+
+def dump_outputs(out_dir, arrays):
+    """Write ``{name: tensor}`` as ``out_dir/<name>.npy`` (float32).  An array above
+    DUMP_MAX_ELEMS elements is written as a sample at fixed positions (seeded by the
+    array's size alone, sorted), the same from run to run and build to build."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().to("cpu", torch.float32).reshape(-1).numpy()
+        if a.size > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.RandomState(a.size % (1 << 32)).choice(a.size, DUMP_MAX_ELEMS, replace=False))
+            a = a[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def run(args):
     from ddim_cold_amd.parallel.dist import (init_distributed, init_single, all_reduce_max, barrier, cleanup,
                                              env_world)
@@ -319,16 +349,20 @@ def run(args):
 
     ms = elapsed / args.steps * 1e3
     value = n * args.batch * args.steps / elapsed
+    if args.dump_outputs and rank == 0:
+        # what train_steps() hands its caller: the last step's loss and the parameters it left
+        phase("dump-outputs")
+        dump_outputs(args.dump_outputs, {"loss": engine.loss_last, "params": engine.flat_p})
     extra = {}
-    if rank == 0 and n == 1 and args.dataset == "cold" and not args.no_gaussian and dev.type == "cuda":
+    full = args.full and rank == 0 and n == 1 and dev.type == "cuda"
+    if full and args.dataset == "cold" and not args.no_gaussian:
         # the reference's other training task (DiffusionDataset, diffusion_loader.py:24-58):
         # Gaussian DDIM, q_sample batch drawn inside the patch-embedding launch, same
         # model / batch / optimizer; timed the same way (outside the headline number)
         phase("extra:gaussian-ddim")
         extra.update(_time_train(args, args.model, "gaussian", dev, lr, seed=43, pool=pool,
                                  prefix="gaussian_ddim_train"))
-    if rank == 0 and n == 1 and args.dataset == "cold" and args.model == "vit_tiny" and not args.no_hires \
-            and dev.type == "cuda":
+    if full and args.dataset == "cold" and args.model == "vit_tiny" and not args.no_hires:
         # BASELINE.json config 4 (the 200x200 high-resolution path) and the
         # sampling CLI's oxford_flower model (ViT.py:277), trained the same way as the
         # headline: same per-GPU batch, full AdamW step, K-step graphs, timed between
@@ -337,7 +371,7 @@ def run(args):
         for name, key in (("vit_small_200", "vit_small_200_train"), ("oxford_flower", "oxford_flower_train")):
             phase(f"extra:{name}")
             extra.update(_time_train(args, name, "cold", dev, lr, seed=44, prefix=key))
-    if rank == 0 and n == 1 and args.dataset == "cold" and not args.no_vendor and dev.type == "cuda":
+    if full and args.dataset == "cold" and not args.no_vendor:
         # same-node vendor comparator: the reference step (multi_gpu_trainer.py:115-134) from stock
         # PyTorch-ROCm ops (hipBLASLt / SDPA / fused AdamW), captured whole in one graph
         from ddim_cold_amd.bench.vendor_baseline import time_vendor_train
@@ -352,7 +386,7 @@ def run(args):
                                         "autocast": "bf16", "final_loss": round(vloss, 5)}
         del vm
     # the sampler metric is a 1-GPU number (BASELINE.json config 5): multi-rank runs skip it
-    if rank == 0 and n == 1 and not args.no_sampler and dev.type == "cuda":
+    if full and not args.no_sampler:
         from ddim_cold_amd.diffusion.samplers import DDIMSampler
         model.eval()
         s = DDIMSampler(model, dev, k=args.sampler_k)

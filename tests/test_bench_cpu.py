@@ -68,6 +68,46 @@ def test_bench_gaussian_dataset_two_ranks_cpu():
     assert "Gaussian DDIM" in out["data"] and out["n_gpus"] == 2 and out["value"] > 0
 
 
+def test_bench_dump_outputs_repeatable_cpu(tmp_path):
+    """--dump-outputs writes the last timed step's loss and the updated parameters as
+    float32 .npy files (64 MB at most in all); the inputs are seeded, so a second run with
+    the same arguments writes the same arrays.  A plain run carries no extra keys."""
+    import numpy as np
+    outs = []
+    for d in ("a", "b"):
+        r = _bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "4", "--dump-outputs",
+                    str(tmp_path / d)])
+        assert r.returncode == 0, r.stderr[-3000:]
+        out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+        assert REQUIRED <= set(out) and out["steps"] == 3 and out["ms_per_step"] > 0
+        assert not [k for k in out if k.startswith(("ddim_sampler", "draft2drawing", "gaussian_ddim", "train_vendor",
+                                                    "vit_small_200", "oxford_flower"))]
+        files = sorted(os.listdir(tmp_path / d))
+        assert files == ["loss.npy", "params.npy"]
+        assert sum(os.path.getsize(tmp_path / d / f) for f in files) <= 64 << 20
+        outs.append({f: np.load(tmp_path / d / f) for f in files})
+        assert abs(float(outs[-1]["loss.npy"][0]) - out["config"]["final_loss"]) < 1e-5
+    for f, a in outs[0].items():
+        assert a.dtype == np.float32 and a.size > 0 and np.isfinite(a).all()
+        np.testing.assert_array_equal(a, outs[1][f])
+    assert outs[0]["params.npy"].std() > 0
+
+
+def test_bench_dump_samples_large_arrays_at_fixed_positions(tmp_path):
+    """An array above the per-array limit is written as a sample at positions that depend
+    on its size alone: equal arrays give equal files, and the sample keeps the order."""
+    import numpy as np
+    import torch
+    import bench
+    t = torch.arange(bench.DUMP_MAX_ELEMS + 1000, dtype=torch.float64)
+    bench.dump_outputs(str(tmp_path / "a"), {"x": t, "small": t[:7]})
+    bench.dump_outputs(str(tmp_path / "b"), {"x": t.clone()})
+    a, b = np.load(tmp_path / "a" / "x.npy"), np.load(tmp_path / "b" / "x.npy")
+    assert a.dtype == np.float32 and a.shape == (bench.DUMP_MAX_ELEMS,)
+    assert (np.diff(a) > 0).all() and np.array_equal(a, b)
+    assert np.array_equal(np.load(tmp_path / "a" / "small.npy"), np.arange(7, dtype=np.float32))
+
+
 def test_bench_stalled_rank_is_named_before_the_deadline_self_spawn():
     """One rank stalls at the timed phase (the other then waits in the collective
     bracket): `bench.py --gpus 2` exits non-zero well before the driver's 600 s and the
