@@ -283,8 +283,6 @@ Tensor qkv_fwd(Tensor a, Tensor w, Tensor b, int64_t B, int64_t N, int64_t H, c1
   return out;
 }
 
-// attention-dropout keep-flag words the short forward stores for the backward
-// (0: this shape takes the long-sequence kernels, which regenerate the masks)
 int64_t gemm_tile_override_op(int64_t cfg) { return gemm_set_tile_override((int)cfg); }
 // GEMM phase stamps (tools/ub_gemm_stamps.py): an int32 buffer, or None to stop
 void gemm_stamps_op(c10::optional<Tensor> buf) {
@@ -296,6 +294,8 @@ void gemm_stamps_op(c10::optional<Tensor> buf) {
   }
 }
 
+// attention-dropout keep-flag words the short forward stores for the backward
+// (0: this shape takes the long-sequence kernels, which regenerate the masks)
 int64_t attn_keep_words_op(int64_t B, int64_t H, int64_t N, int64_t hd) {
   return attn_keep_words((int)B, (int)H, (int)N, (int)hd);
 }

@@ -241,73 +241,16 @@ void comm_destroy(int64_t h) {
   g_comms[h] = nullptr;
 }
 
-// ---- external graph events (the engine's event-split step, engine.py comm_events)
-// A compute graph records one event per gradient bucket as an event-record node
-// appended to the capture by hand (hipGraphAddEventRecordNode on the capturing
-// stream's current dependencies, which then become that node): the graph stays a
-// single chain, and the host-issued collectives on the comm stream wait on those
-// events after the replay is enqueued.  (torch.cuda.Event(external=True) is refused
-// on ROCm builds, and hipEventRecordWithFlags(.., hipEventRecordExternal) returns
-// invalid-argument inside a capture on this runtime.)
-#define HIP_CHECK(cmd)                                                                   \
-  do {                                                                                   \
-    hipError_t e_ = (cmd);                                                               \
-    TORCH_CHECK(e_ == hipSuccess, "HIP error ", hipGetErrorString(e_), " at ", #cmd);    \
-  } while (0)
-
-// flags: extra hipEventCreateWithFlags bits on top of hipEventDisableTiming, e.g.
-// hipEventReleaseToDevice (device-scope release: visible to the comm queue of the
-// same GPU, which is all the bucket's collective needs) or hipEventDisableSystemFence
-// -- the default system-scope fence writes back AND invalidates the L2s, and the
-// compute kernels after it refill them.
-int64_t event_create(int64_t flags) {
-  hipEvent_t ev;
-  HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming | static_cast<unsigned>(flags)));
-  return reinterpret_cast<int64_t>(ev);
-}
-
-void event_record_external(int64_t ev) {
-  hipStream_t s = c10::hip::getCurrentHIPStream().stream();
-  hipEvent_t e = reinterpret_cast<hipEvent_t>(ev);
-  hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-  hipGraph_t g = nullptr;
-  const hipGraphNode_t* deps = nullptr;
-  size_t nd = 0;
-  HIP_CHECK(hipStreamGetCaptureInfo_v2(s, &st, nullptr, &g, &deps, &nd));
-  if (st != hipStreamCaptureStatusActive) {
-    HIP_CHECK(hipEventRecord(e, s));
-    return;
-  }
-  std::vector<hipGraphNode_t> dv(deps, deps + nd);
-  hipGraphNode_t node;
-  HIP_CHECK(hipGraphAddEventRecordNode(&node, g, dv.data(), dv.size(), e));
-  HIP_CHECK(hipStreamUpdateCaptureDependencies(s, &node, 1, hipStreamSetCaptureDependencies));
-}
-
-void stream_wait_event(int64_t ev) {
-  HIP_CHECK(hipStreamWaitEvent(c10::hip::getCurrentHIPStream().stream(), reinterpret_cast<hipEvent_t>(ev), 0));
-}
-
-void event_destroy(int64_t ev) { HIP_CHECK(hipEventDestroy(reinterpret_cast<hipEvent_t>(ev))); }
-
-// ---- counter hand-off (engine.py comm_signal="flag"): the compute graph bumps a
-// per-bucket uint32 counter with a kernel node; the comm stream waits until the
-// counter reaches the replay number (wait-value packet, >=).
+// ---- counter hand-off (the engine's event-split step, engine.py comm_events): the
+// compute graph bumps a per-bucket uint32 counter with a kernel node (flag_bump); the
+// comm stream waits until the counter reaches the replay number (flag_wait).
 void flag_bump(Tensor flags, int64_t k) {
   TORCH_CHECK(flags.is_cuda() && flags.scalar_type() == at::kInt && flags.is_contiguous(), "flags: int32 cuda");
   TORCH_CHECK(k >= 0 && k < flags.numel(), "flag index out of range");
   flag_bump_launch(flags.data_ptr(), (int)k, c10::hip::getCurrentHIPStream().stream());
 }
 
-void stream_wait_flag(Tensor flags, int64_t k, int64_t value) {
-  TORCH_CHECK(flags.is_cuda() && flags.scalar_type() == at::kInt && flags.is_contiguous(), "flags: int32 cuda");
-  TORCH_CHECK(k >= 0 && k < flags.numel(), "flag index out of range");
-  HIP_CHECK(hipStreamWaitValue32(c10::hip::getCurrentHIPStream().stream(),
-                                 reinterpret_cast<uint32_t*>(flags.data_ptr<int>() + k),
-                                 static_cast<uint32_t>(value), hipStreamWaitValueGte, 0xFFFFFFFFu));
-}
-
-// the same wait as a 1-lane polling kernel of ours (bounded, raises err[0] on timeout)
+// a 1-lane polling kernel (>=, bounded; raises err[0] on timeout)
 void flag_wait(Tensor flags, int64_t k, int64_t value, Tensor err, int64_t timeout_us) {
   TORCH_CHECK(flags.is_cuda() && flags.scalar_type() == at::kInt && flags.is_contiguous(), "flags: int32 cuda");
   TORCH_CHECK(err.is_cuda() && err.scalar_type() == at::kInt && err.numel() >= 1, "err: int32 cuda");
@@ -334,22 +277,10 @@ void pair_all_reduce_(Tensor buf, Tensor stage, Tensor flags, int64_t e, Tensor 
 
 int64_t pair_flags_size() { return pair_allreduce_flags(); }
 
-bool stream_wait_value_supported(int64_t device) {
-  int v = 0;
-  if (hipDeviceGetAttribute(&v, hipDeviceAttributeCanUseStreamWaitValue, (int)device) != hipSuccess) return false;
-  return v != 0;
-}
-
 }  // namespace
 
 TORCH_LIBRARY_FRAGMENT(ddim_cold, m) {
-  m.def("event_create(int flags=0) -> int", &event_create);
-  m.def("event_record_external(int event) -> ()", &event_record_external);
-  m.def("stream_wait_event(int event) -> ()", &stream_wait_event);
-  m.def("event_destroy(int event) -> ()", &event_destroy);
   m.def("flag_bump(Tensor(a!) flags, int k) -> ()", &flag_bump);
-  m.def("stream_wait_flag(Tensor flags, int k, int value) -> ()", &stream_wait_flag);
-  m.def("stream_wait_value_supported(int device) -> bool", &stream_wait_value_supported);
   m.def("flag_wait(Tensor flags, int k, int value, Tensor(a!) err, int timeout_us=0) -> ()", &flag_wait);
   m.def("pair_all_reduce_(Tensor(a!) buf, Tensor(b!) stage, Tensor(c!) flags, int e, Tensor(d!) err, "
         "int timeout_us=0) -> ()", &pair_all_reduce_);

@@ -52,9 +52,9 @@ __global__ __launch_bounds__(kThreads) void wire_unpack_kernel(const bf16* __res
 }
 
 // Bucket hand-off signal of the event-split data-parallel step (engine.py,
-// comm_signal="flag"): one lane adds 1 to flags[k] with a system-scope release,
+// comm_events): one lane adds 1 to flags[k] with a system-scope release,
 // i.e. after every earlier write of this queue's kernels is visible device-wide;
-// the comm stream waits for the counter with a stream wait-value packet.  A plain
+// the comm stream waits for the counter with flag_wait_kernel below.  A plain
 // kernel node, unlike an event-record node, keeps the compute graph one
 // uninterrupted chain.  Vector-memory atomic (lane-indexed address).
 __global__ __launch_bounds__(64) void flag_bump_kernel(unsigned int* __restrict__ flags, int k) {

@@ -265,7 +265,7 @@ __device__ __forceinline__ void gemm_dma_body(const GemmParams& p, int tm, int t
   // vector epilogues take the SWAPPED accumulator layout: mfma(B, A) = C^T puts 4
   // consecutive output columns of one row in each lane, no quad transpose.
   constexpr bool VEC = UsesVecEpi<EPI>::value;
-  VecEpi<EPI, FM, FN, false, VEC> ep;
+  VecEpi<EPI, FM, FN, VEC> ep;
   if (VEC) ep.prefetch(p, m0 + wm * TM, n0 + wn * TN, g, li);
 
   // main loop; the bias-gradient MFMA variant is a separate instantiation so the
@@ -563,7 +563,7 @@ static int pick_tiles(int M, int N, int K, int splits, bool at, bool bt, bool wi
 
 template <bool AT, bool BT, int EPI>
 static void launch_auto(GemmParams p, int splits, hipStream_t stream) {
-  const bool dma_ok = (AT || BT || p.K % 64 == 0) && (AT || p.K % 64 == 0);
+  const bool dma_ok = AT || p.K % 64 == 0;
   if (dma_ok) {
     // DGELU (input gradient through GELU + dropout, bf16 out) stays on 4-wave tiles at
     // every measured M (M = 20,032: 25.5 vs 26.5 us; 40,064: 42.1 vs 49.9)

@@ -2,12 +2,6 @@
 // consumer/producer, QKV head-major scatter, residual + dropout + drop-path,
 // GELU, head / unpatchify / loss / DDIM update, patch embedding, gradient
 // accumulate), shared by every GEMM kernel of gemm.hip.
-//
-// ``PUB`` (VecEpi, off in every current kernel): the epilogue's hand-off outputs
-// (bf16 residual copy, LayerNorm statistics, GELU output) are stored
-// write-through (sc1) and the statistics it consumes are loaded sc1, for a
-// consumer workgroup of the SAME launch on another XCD (MI355X_MICROARCH.md,
-// inter-workgroup visibility).
 #pragma once
 #include "common.h"
 #include "kernels.h"
@@ -511,27 +505,8 @@ __device__ __forceinline__ float2 stat4(const f32x4& v) {
                      __builtin_fmaf(v[0], v[0], v[1] * v[1]) + __builtin_fmaf(v[2], v[2], v[3] * v[3]));
 }
 
-// bf16x4 store, write-through (sc1) when the bytes are handed to another workgroup of the launch
-template <bool PUB>
-__device__ __forceinline__ void st4bf_pub(bf16* p, const f32x4& v) {
-  if (!PUB) {
-    st4bf(p, v);
-  } else {
-    bf16x4 b;
-    b[0] = f2bf(v[0]); b[1] = f2bf(v[1]); b[2] = f2bf(v[2]); b[3] = f2bf(v[3]);
-    st8_sc1(p, __builtin_bit_cast(uint64_t, b));
-  }
-}
-template <bool PUB>
-__device__ __forceinline__ void st2f_pub(float* p, float2 v) {
-  if (!PUB) *reinterpret_cast<float2*>(p) = v;
-  else st8_sc1(p, __builtin_bit_cast(uint64_t, v));
-}
-template <bool PUB>
-__device__ __forceinline__ float2 ld2f_pub(const float* p) {
-  if (!PUB) return *reinterpret_cast<const float2*>(p);
-  return __builtin_bit_cast(float2, ld8_sc1(p));
-}
+__device__ __forceinline__ void st2f(float* p, float2 v) { *reinterpret_cast<float2*>(p) = v; }
+__device__ __forceinline__ float2 ld2f(const float* p) { return *reinterpret_cast<const float2*>(p); }
 __device__ __forceinline__ f32x4 ld4bf(const bf16* p) {
   const bf16x4 b = *reinterpret_cast<const bf16x4*>(p);
   return f32x4{bf2f(b[0]), bf2f(b[1]), bf2f(b[2]), bf2f(b[3])};
@@ -554,7 +529,7 @@ __device__ __forceinline__ f32x4 ld4bf(const bf16* p) {
 // pre-activation, embeddings, accumulate target) can be issued BEFORE the main
 // loop (`prefetch`) and land while the MFMAs run: at these sizes a GEMM is a
 // chain of ~3 dependent memory round trips and this removes one of them.
-template <int EPI, int FM, int FN, bool PUB = false, bool SW = false>
+template <int EPI, int FM, int FN, bool SW = false>
 struct VecEpi {
   static constexpr bool PRE = EPI == EPI_RESID || EPI == EPI_DGELU || EPI == EPI_EMBED || EPI == EPI_ACC ||
                               EPI == EPI_HEADR || EPI == EPI_HEADL;
@@ -638,7 +613,7 @@ struct VecEpi {
 #pragma unroll
       for (int k = 0; k < LN_MAX_SLOTS / 4; ++k) {
         const int sl = q + 4 * k;
-        lnst[i][k] = (fold && m < p.M && sl < np_in) ? ld2f_pub<PUB>(p.ln_st + 2 * ((size_t)m * np_in + sl))
+        lnst[i][k] = (fold && m < p.M && sl < np_in) ? ld2f(p.ln_st + 2 * ((size_t)m * np_in + sl))
                                                      : make_float2(0.f, 0.f);
       }
     }
@@ -779,7 +754,7 @@ struct VecEpi {
           st4(reinterpret_cast<float*>(p.C) + idx, v);
           if (prod) {
             part[i][j / 2] = f2add(part[i][j / 2], stat4(v));
-            st4bf_pub<PUB>(p.xb_out + idx, v);
+            st4bf(p.xb_out + idx, v);
           }
         } else if (EPI == EPI_GELU) {
           st4bf(reinterpret_cast<bf16*>(p.C) + idx, v);
@@ -792,7 +767,7 @@ struct VecEpi {
             if (p.thr_drop) e = kp[c] ? e * p.scale_drop : 0.f;
             h[c] = e;
           }
-          st4bf_pub<PUB>(reinterpret_cast<bf16*>(p.C2) + idx, h);
+          st4bf(reinterpret_cast<bf16*>(p.C2) + idx, h);
         } else if (EPI == EPI_DGELU) {
           bool kp[4] = {true, true, true, true};
           if (p.thr_drop) dropout_keep4(salt_drop, (uint32_t)idx, p.thr_drop, kp);
@@ -844,7 +819,7 @@ struct VecEpi {
           st4(reinterpret_cast<float*>(p.C) + idx, v);
           if (prod) {
             part[i][j / 2] = f2add(part[i][j / 2], stat4(v));
-            st4bf_pub<PUB>(p.xb_out + idx, v);
+            st4bf(p.xb_out + idx, v);
           }
         }
       }
@@ -871,7 +846,7 @@ struct VecEpi {
         st4(reinterpret_cast<float*>(p.C) + idx, v);
         if (prod) {
           cpart[j / 2] = f2add(cpart[j / 2], stat4(v));
-          st4bf_pub<PUB>(p.xb_out + idx, v);
+          st4bf(p.xb_out + idx, v);
         }
       }
       if (prod) {
@@ -881,7 +856,7 @@ struct VecEpi {
           float2 t = cpart[sl];
           t = rowsum<1>(rowsum<0>(t));
           if (sharer(g, li) == 0 && cls_i >= 0)
-            st2f_pub<PUB>(p.st_out + 2 * ((size_t)b * (p.tokens + 1) * np_out + colbase / LN_SLOT + sl), t);
+            st2f(p.st_out + 2 * ((size_t)b * (p.tokens + 1) * np_out + colbase / LN_SLOT + sl), t);
         }
       }
     }
@@ -903,8 +878,7 @@ struct VecEpi {
           float2 t = part[i][sl];
           t = rowsum<1>(rowsum<0>(t));
           if (sharer(g, li) == 0 && rowm[i] >= 0)
-            st2f_pub<PUB>(p.st_out + 2 * ((size_t)fold_token_row<EPI>(p, rowm[i]) * np_out + colbase / LN_SLOT + sl),
-                          t);
+            st2f(p.st_out + 2 * ((size_t)fold_token_row<EPI>(p, rowm[i]) * np_out + colbase / LN_SLOT + sl), t);
         }
     }
   }

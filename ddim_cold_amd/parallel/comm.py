@@ -31,44 +31,13 @@ def _store():
     return dist.distributed_c10d._get_default_store()
 
 
-class ExternalEvent:
-    """A HIP event recorded as an external event-record node when captured: the
-    capturing graph keeps a single chain (no cross-stream branch), and a stream
-    that waits on the event after the graph's replay is enqueued orders after that
-    point of the replay (``csrc/comm.cpp`` event_*)."""
-
-    RELEASE_TO_DEVICE = 0x40000000     # hipEventReleaseToDevice
-    DISABLE_SYSTEM_FENCE = 0x20000000  # hipEventDisableSystemFence
-
-    def __init__(self, flags: int = 0):
-        _ext.load(raise_on_error=True)
-        self.handle = int(torch.ops.ddim_cold.event_create(int(flags)))
-
-    def record(self):
-        """Record on the current stream (inside a capture: an external node)."""
-        torch.ops.ddim_cold.event_record_external(self.handle)
-
-    def wait(self, stream: torch.cuda.Stream):
-        with torch.cuda.stream(stream):
-            torch.ops.ddim_cold.stream_wait_event(self.handle)
-
-    def __del__(self):
-        h = getattr(self, "handle", None)
-        if h is not None:
-            try:
-                torch.ops.ddim_cold.event_destroy(h)
-            except Exception:  # interpreter shutdown
-                pass
-            self.handle = None
-
-
 class FlagSignal:
     """Per-bucket hand-off counters for the event-split data-parallel step.
 
     Inside the compute graph, :meth:`bump` is a 1-lane kernel node that adds 1 to
     ``flags[k]`` with a system-scope release once the bucket's gradients are final;
     the host then orders a comm-stream collective behind ``flags[k] >= replays``
-    with a bounded polling kernel (:meth:`waiter`).  Unlike an event-record node,
+    with a bounded polling kernel (:meth:`wait`).  Unlike an event-record node,
     the kernel node keeps the graph one uninterrupted chain (measured on MI355X:
     the comm stream waiting on mid-graph event nodes started only after the whole
     graph had finished, so nothing overlapped)."""
@@ -84,25 +53,15 @@ class FlagSignal:
         # hand-off times out (exercises the failure path end to end)
         self.skew = int(os.environ.get("DDIM_COLD_TEST_HANDOFF_SKEW", "0"))
 
-    @staticmethod
-    def supported(device) -> bool:
-        _ext.load(raise_on_error=True)
-        d = torch.device(device)
-        return bool(torch.ops.ddim_cold.stream_wait_value_supported(d.index if d.index is not None else
-                                                                     torch.cuda.current_device()))
-
     def bump(self, k: int):
         torch.ops.ddim_cold.flag_bump(self.flags, int(k))
 
-    def waiter(self, k: int):
-        sig = self
-
-        class _Wait:
-            def wait(self_, stream):
-                with torch.cuda.stream(stream):  # our bounded 1-lane polling kernel
-                    torch.ops.ddim_cold.flag_wait(sig.flags, int(k), int(sig.expected + sig.skew) & 0xFFFFFFFF,
-                                                  sig.err, sig.timeout_us)
-        return _Wait()
+    def wait(self, k: int, stream: torch.cuda.Stream):
+        """Order ``stream`` behind bucket ``k``'s counter reaching the current replay
+        number: our bounded 1-lane polling kernel."""
+        with torch.cuda.stream(stream):
+            torch.ops.ddim_cold.flag_wait(self.flags, int(k), int(self.expected + self.skew) & 0xFFFFFFFF,
+                                          self.err, self.timeout_us)
 
     def failed(self) -> bool:
         return int(self.err.item()) != 0

@@ -10,33 +10,33 @@ AdamW step, cosine LR step, zero_grad) re-designed for a latency-bound
   in two more, plus a bf16 shadow of the parameters that the MFMA GEMMs read.
   Every param offset is 256-B aligned.  All-reduce buckets are contiguous arena
   ranges: no pack/unpack kernels.
-* **Fused optimizer.**  3 launches per step (global grad-norm, AdamW + clip +
-  cosine LR + bf16 shadow refresh + grad zeroing, counter bump); the LR /
-  Adam step / RNG step live in device memory so the step is graph-replayable.
+* **Fused optimizer.**  One launch: AdamW + clip + cosine LR + bf16 shadow refresh +
+  grad zeroing.  The grad-norm partials come from the weight-gradient launch's
+  epilogues (data parallel: one pass over the reduced arena); the loss EMA and the
+  counter bump ride in the LayerNorm-fold launch that follows.  The LR / Adam
+  step / RNG step live in device memory so the step is graph-replayable.
 * **Deferred weight gradients.**  Single process: every weight-gradient GEMM
-  of the step is ONE launch after the embedding backward
-  (``ops.linear_wgrad_multi``, 1,548 64x64 tiles, no token split, no atomics).
-  Data parallel: one such launch per gradient bucket, so each bucket's
-  all-reduce can start while the remaining blocks run backward.  (Issuing them
-  on a side stream measured slower: 28.2k vs 33.1k img/s.)
-* **hipGraphs per step, bucketed RCCL all-reduce between them.**  Gradient
-  buckets are contiguous arena ranges closed at transformer-block boundaries
-  of the backward; as soon as a bucket's gradients are final its
-  ``all_reduce`` (RCCL over xGMI via ``torch.distributed`` 'nccl') runs on
-  a communication stream, so it overlaps the backward of the remaining
-  blocks, and the optimizer waits on that stream.  Data parallel default
-  (``comm_events``): forward + backward is ONE linear graph that bumps a
-  per-bucket counter at every bucket boundary (a 1-lane kernel node), the
-  optimizer a second; each bucket's collective waits on the comm stream
-  behind a bounded polling kernel for its counter, queued ahead of the
-  compute replay (a comm branch inside the graph costs ~30 us per fork on
-  MI355X; event-record nodes delayed the comm work to the end of the graph).  ``autotune_comm()`` picks the bucket layout (or one
-  inline all-reduce) by measuring on the job's own ranks.  Alternatives:
-  collectives captured into the step graph (``graph_comm``) or
-  ``n_buckets + 1`` graph segments with host-issued collectives in between.
-  Buckets default to ~2 blocks (~7 MB fp32 for ViT-tiny): few enough
-  collectives for the per-call latency of 7-link point-to-point xGMI rings,
-  large enough to overlap.  Inactive time-embedding rows are not reduced.
+  of the step is ONE launch after the backward (``ops.linear_wgrad_multi``,
+  1,548 64x64 tiles, no token split, no atomics).  Data parallel: one such launch
+  per gradient bucket, so each bucket's all-reduce can start while the remaining
+  blocks run backward.  (On a side stream they measured slower: 28.2k vs 33.1k img/s.)
+* **hipGraphs per step, bucketed RCCL all-reduce.**  Single process: the step is
+  ONE graph.  Data parallel: gradient buckets are contiguous arena ranges closed
+  at transformer-block boundaries of the backward; as soon as a bucket's
+  gradients are final its ``all_reduce`` (RCCL over xGMI) runs on a communication
+  stream, overlapping the backward of the remaining blocks, and the optimizer
+  waits on that stream.  Default (``comm_events``), the event-split step: forward
+  + backward is one linear graph that bumps a per-bucket counter at every bucket
+  boundary (a 1-lane kernel node), the optimizer a second; the host issues each
+  bucket's collective on the comm stream behind a bounded polling kernel for its
+  counter, queued ahead of the compute replay.  Alternatives: collectives
+  captured into the one step graph (``graph_comm``; a comm branch costs ~30 us
+  per fork on MI355X) or ``n_buckets + 1`` graph segments with host-issued
+  collectives in between.  ``autotune_comm()`` picks the bucket layout (or one
+  inline all-reduce) by measuring on the job's own ranks.  Buckets default to
+  ~2 blocks (~7 MB fp32 for ViT-tiny): few enough collectives for the per-call
+  latency of 7-link point-to-point xGMI rings, large enough to overlap.  Inactive
+  time-embedding rows are not reduced.
 """
 from __future__ import annotations
 
@@ -60,6 +60,10 @@ ALIGN = 64  # elements (256 B fp32)
 # mode a watchdog poll inside the capture window was seen on MI355X to invalidate
 # the capture (fallback to segments) and abort the process from the watchdog.
 CAPTURE_MODE = "thread_local"
+# how a captured step replays (TrainEngine._capture): ONE graph (single process, or
+# the collectives captured in it; K-step graphs too), the event-split pair, or one
+# graph segment per gradient bucket; the last two with host-issued collectives
+SINGLE, EVENT_SPLIT, SEGMENTS = "single", "event-split", "segments"
 # event-split data parallel with counter hand-offs: queue the comm stream's work
 # ahead of the compute-graph replay (DDIM_COLD_PREISSUE=0: behind it)
 PREISSUE = os.environ.get("DDIM_COLD_PREISSUE", "1") != "0"
@@ -146,23 +150,24 @@ class EngineConfig:
     # pairs (49 KB per rank for ViT-tiny at batch 32) instead of all-reducing the
     # dense [2000, 384] table (3.1 MB).  SURVEY.md §5.8 option 4.
     temb_sparse: bool = True
-    # capture the bucketed all-reduces INTO the step's hipGraph (RCCL kernels on a
-    # comm-stream branch joined before the optimizer) instead of replaying one
-    # graph segment per bucket with host-issued collectives in between.
-    # Measured on one MI355X with a 1-rank RCCL group: 0.998 ms/step captured vs
-    # 1.125 segmented (each extra graph launch + stream join costs ~30 us).
-    # Falls back to segments if the capture raises.
+    # data parallel without comm_events: capture the bucketed all-reduces INTO the
+    # step's one hipGraph (RCCL kernels on a comm-stream branch joined before the
+    # optimizer) instead of replaying one graph segment per bucket with host-issued
+    # collectives in between.  Measured on one MI355X with a 1-rank RCCL group:
+    # 0.998 ms/step captured vs 1.125 segmented (each extra graph launch + stream join
+    # costs ~30 us).  Falls back to segments if the capture raises.
     graph_comm: bool = True
-    # data parallel, the default capture: the step's compute as TWO linear graphs
-    # (forward + backward, then optimizer) whose only cross-stream edges are
-    # external event-record nodes at the bucket boundaries; the collectives are
-    # issued by the host on the comm stream (eager RCCL, nothing of it captured),
-    # each waiting on its bucket's event.  A graph with a comm-stream branch
-    # (graph_comm) costs ~30-35 us per fork on MI355X -- measured on one GPU with a
-    # 1-element kernel on a side stream at each of the 5 bucket boundaries: 0.818 ->
-    # 1.013 ms/step -- and with one elementwise pass per bucket on the comm stream
-    # (standing in for the collective) the event-split step runs at 0.937 vs 1.072
-    # captured.  False: graph_comm / segments.
+    # data parallel, the default capture (event-split): the step's compute as TWO linear
+    # graphs (forward + backward, then optimizer); the collectives are issued by the
+    # host (eager RCCL, nothing of it captured), on the comm stream each behind a
+    # polling kernel for the per-bucket counter that a 1-lane kernel node of the compute
+    # graph bumps at the bucket's boundary, or (comm_inline) on the compute stream
+    # between the two graphs.  A graph with a comm-stream branch (graph_comm) costs
+    # ~30-35 us per fork on MI355X -- measured on one GPU with a 1-element kernel on a
+    # side stream at each of the 5 bucket boundaries: 0.818 -> 1.013 ms/step -- and with
+    # one elementwise pass per bucket on the comm stream (standing in for the
+    # collective) the event-split step runs at 0.937 vs 1.072 captured.  False:
+    # graph_comm / segments.
     comm_events: bool = True
     # data parallel: issue the collectives on the compute stream (no comm stream, no
     # overlap; with comm_events, host-issued between the two step graphs).  With one
@@ -231,7 +236,6 @@ class TrainEngine:
         # created later could land on a hardware queue another stream already holds)
         self._comm_obj = self._comm_stream() if (self.is_cuda and self.segmented) else None
         self.comm = None if cfg.comm_inline else self._comm_obj
-        self.handoff_order: Optional[str] = None  # event-split step: "pre-issued" / "post-replay"
         self.comm_choice: Optional[str] = None  # autotune_comm() winner
         self.comm_times: Dict[str, float] = {}
         if cfg.comm not in ("torch", "native", "auto"):
@@ -248,10 +252,18 @@ class TrainEngine:
         elif cfg.comm == "auto" and self.dist_on and self.is_cuda and default_pg:
             self.ncomm = self._try_native(dev)
         self.comm_backend = "native" if self.ncomm is not None else "torch"
+        # the captured step: written by _capture(), cleared by _drop_capture() only
         self._graphs: Optional[List[torch.cuda.CUDAGraph]] = None
-        self._graph_comm_failed = False  # captured collectives refused -> per-bucket segments
+        self._mode: Optional[str] = None  # how _graphs replay: SINGLE / EVENT_SPLIT / SEGMENTS
         self._multi = None  # (K-step graph, K) for train_steps
+        self._signal = None  # event-split step with a comm stream: the buckets' FlagSignal
+        # event-split step: "pre-issued" / "post-replay" (comm stream), "inline" (none)
+        self.handoff_order: Optional[str] = None
+        self._graph_comm_failed = False  # captured collectives refused -> per-bucket segments
         self._eager_steps = 0
+        self.comm_fit = None  # probe_allreduce()'s fitted all-reduce model
+        self._snap = None  # snapshot_to_host() buffers
+        self._sched_template = None  # scheduler_state_dict() key layout
         self.batch_fn: Optional[Callable] = None
         self._static = None
         self.steps_done = 0
@@ -351,19 +363,16 @@ class TrainEngine:
         that bucket's collective then ran on gradients that were not final yet, so the
         replicas may have diverged -- the run must stop (and resume from a checkpoint),
         not continue.  One host sync; call at log points, not every step."""
-        sig = getattr(self, "_signal", None)
-        if sig is not None:
-            sig.check()
+        if self._signal is not None:
+            self._signal.check()
 
     def comm_error(self) -> bool:
         """True if a hand-off wait has timed out since the last :meth:`reset_comm_error`."""
-        sig = getattr(self, "_signal", None)
-        return sig is not None and sig.failed()
+        return self._signal is not None and self._signal.failed()
 
     def reset_comm_error(self):
-        sig = getattr(self, "_signal", None)
-        if sig is not None:
-            sig.err.zero_()
+        if self._signal is not None:
+            self._signal.err.zero_()
 
     def attach_comm(self, comm, world: int):
         """Drive the gradient exchange through ``comm`` (the ``all_reduce_`` of a
@@ -381,8 +390,7 @@ class TrainEngine:
         self.ncomm = comm
         self.world = int(world)
         self.comm_backend = type(comm).__name__
-        self._graphs = None
-        self._multi = None
+        self._drop_capture(rewarm=False)
 
     def close(self):
         """Release the native communicator (before the process group is destroyed)."""
@@ -468,6 +476,7 @@ class TrainEngine:
                              weights={n: self.flat_pb[o:o + k].view(p.shape)
                                       for n, p in named for o, k in [self.offsets[n]] if is_matrix_param(n)}) \
             if _program.FOLD_LN else None
+        self.wt = None
         self._refresh_shadow()
         for n, p in named:
             o, k = self.offsets[n]
@@ -475,7 +484,6 @@ class TrainEngine:
         self.param_tensors: ModelTensors = collect(views_p, c.depth, c.dim)
         if self.lnfold is not None:
             self.lnfold.attach(self.param_tensors)
-        self.wt = None
         if self.is_cuda and c.tokens >= TRANSPOSED_DGRAD_MIN_TOKENS:
             self.wt = TransposedShadows(self.param_tensors)
             self.wt.attach(self.param_tensors)
@@ -612,17 +620,16 @@ class TrainEngine:
 
     def _refresh_shadow(self):
         self.flat_pb.copy_(self.flat_p.to(torch.bfloat16))
-        if getattr(self, "lnfold", None) is not None:
+        if self.lnfold is not None:
             self.lnfold.refresh()
-        if getattr(self, "wt", None) is not None:
+        if self.wt is not None:
             self.wt.refresh()
 
     # ------------------------------------------------------------------ step program
     def set_batch_fn(self, fn: Callable):
         """``fn() -> (x_t, target, t)`` device tensors; called inside the captured region."""
         self.batch_fn = fn
-        self._graphs = None
-        self._multi = None
+        self._drop_capture(rewarm=False)
 
     def _grad_overwrite(self, k_acc: int, deferred: bool, ln_final) -> bool:
         """One micro-batch, deferred weight gradients (the single-process tail launch or
@@ -749,10 +756,11 @@ class TrainEngine:
         self.prog._keep = None
         yield ("done", -1)
 
-    def _allreduce(self, k: int, after=None):
-        """Issue bucket ``k``'s collectives on the comm stream, ordered after the
-        current stream (or after the event ``after``: the bucket's boundary inside
-        the replayed compute graph)."""
+    def _allreduce(self, k: int, wait_counter: bool = False):
+        """Issue bucket ``k``'s collectives: on the comm stream, ordered after the
+        current stream (``wait_counter``: after the bucket's counter instead, bumped at
+        its boundary inside the replayed compute graph), or with no comm stream right
+        here on the current stream."""
         if self.ncomm is None and (not self.dist_on or (self.world <= 1 and not self.cfg.force_segments)):
             return
         ranges = self.bucket_ranges[k]
@@ -786,8 +794,8 @@ class TrainEngine:
                 self._temb_exchange()
 
         if self.comm is not None:
-            if after is not None:
-                after.wait(self.comm)
+            if wait_counter:
+                self._signal.wait(k, self.comm)
             else:
                 self.comm.wait_stream(torch.cuda.current_stream(self.device))
             with torch.cuda.stream(self.comm):
@@ -960,7 +968,7 @@ class TrainEngine:
         ring model of this world size."""
         from ..parallel import costmodel as cm
         if model is None:
-            model = getattr(self, "comm_fit", None) or cm.xgmi_ring_model(max(2, min(self.world, 8)))
+            model = self.comm_fit or cm.xgmi_ring_model(max(2, min(self.world, 8)))
         return cm.plan_buckets(self.step_profile(), model)
 
     def candidate_layouts(self):
@@ -998,11 +1006,7 @@ class TrainEngine:
         self._build_buckets()
         if self.is_cuda and self.segmented:
             self.comm = None if self.cfg.comm_inline else self._comm_obj
-        self._graphs = None
-        self._multi = None
-        self._events = None
-        self._signal = None
-        self._eager_steps = 0
+        self._drop_capture(rewarm=True)
         self._graph_comm_failed = False
 
     def _snapshot_state(self):
@@ -1154,73 +1158,82 @@ class TrainEngine:
             break
         raise RuntimeError(f"data parallel: even the eager inline all-reduce step failed ({err}); {reason}")
 
-    def _run_eager(self):
-        gen = self._step_iter()
-        for kind, k in gen:
-            if kind == "bucket":
-                self._allreduce(k)
-                if k == len(self.buckets) - 1:
-                    self._join_comm()
-
-    def _capture(self):
-        if self.segmented and self.cfg.comm_events:
-            self._capture_impl(graph_comm=False, events=True)
-            return
-        if self.segmented and self.cfg.graph_comm and not self._graph_comm_failed:
-            try:
-                self._capture_impl(graph_comm=True)
-                return
-            except Exception as e:  # pragma: no cover - depends on the RCCL build
-                if (self.comm_choice or "").startswith("graph-"):
-                    # a captured layout was asked for (autotune candidate or explicit): its
-                    # failure must reach autotune_comm / the caller, not be timed as segments
-                    raise
-                import warnings
-                warnings.warn(f"capturing collectives in the step graph failed ({e!r}); "
-                              "falling back to per-bucket graph segments")
-                self._graph_comm_failed = True
-                torch.cuda.synchronize(self.device)
-        self._capture_impl(graph_comm=False)
-
-    def _captured_step_body(self):
-        """One whole step issued on the capturing stream (collectives as graph nodes)."""
+    def _run_step(self):
+        """One whole step issued on the current stream: eagerly, or inside the capture
+        of a single step graph (the collectives then become graph nodes)."""
         for kind, k in self._step_iter():
             if kind == "bucket":
                 self._allreduce(k)
                 if k == len(self.buckets) - 1:
                     self._join_comm()
 
-    def _capture_impl(self, graph_comm: bool, events: bool = False):
+    def _drop_capture(self, rewarm: bool):
+        """Forget the captured step: its graphs, the K-step graph, the hand-off
+        counters (``check_comm`` / ``comm_error`` then see none) and ``handoff_order``.
+        The next ``train_step`` re-captures, after ``graph_warmup`` fresh eager steps
+        if ``rewarm``.  Nothing else clears these fields."""
+        self._graphs = None
+        self._mode = None
+        self._multi = None
+        self._signal = None
+        self.handoff_order = None
+        if rewarm:
+            self._eager_steps = 0
+
+    def _capture(self):
+        """Capture the step in the mode the configuration resolves to and record the
+        mode with the graphs; :meth:`_replay` dispatches on that record.  Captured
+        collectives (``graph_comm``) that the RCCL build refuses fall back to
+        per-bucket segments, for this and every later capture of the layout."""
+        if not self.segmented:
+            mode = SINGLE
+        elif self.cfg.comm_events:
+            mode = EVENT_SPLIT
+        elif self.cfg.graph_comm and not self._graph_comm_failed:
+            mode = SINGLE
+        else:
+            mode = SEGMENTS
+        try:
+            self._capture_as(mode)
+        except Exception as e:  # pragma: no cover - depends on the RCCL build
+            # a captured layout that was asked for (autotune candidate or explicit): its
+            # failure must reach autotune_comm / the caller, not be timed as segments
+            if not (self.segmented and mode == SINGLE) or (self.comm_choice or "").startswith("graph-"):
+                raise
+            import warnings
+            warnings.warn(f"capturing collectives in the step graph failed ({e!r}); "
+                          "falling back to per-bucket graph segments")
+            self._graph_comm_failed = True
+            torch.cuda.synchronize(self.device)
+            self._capture_as(SEGMENTS)
+
+    def _capture_as(self, mode: str):
         from ..utils.observe import drain_before_capture, no_gc
         if self.dist_on and self.is_cuda:
             # the warm-up's eager collectives finished on every rank (and dropped by
             # the process-group watchdog) before the capture opens
             drain_before_capture(self.device)
+        multi = sig = order = None
         with no_gc():
-            if events:
-                self._capture_event_graphs()
+            if mode == SINGLE:
+                graphs, multi = self._capture_single()
+            elif mode == EVENT_SPLIT:
+                graphs, sig = self._capture_event_split()
+                order = "inline" if sig is None else "pre-issued" if self._preissue_ok() else "post-replay"
             else:
-                self._capture_graphs(graph_comm)
+                graphs = self._capture_segments()
+        self._graphs, self._mode, self._multi, self._signal, self.handoff_order = graphs, mode, multi, sig, order
 
-    def _capture_event_graphs(self):
-        """Compute graph (forward + backward, an external event recorded at every
-        bucket boundary) + optimizer graph; see ``EngineConfig.comm_events``."""
+    def _capture_event_split(self):
+        """Compute graph (forward + backward) + optimizer graph; see
+        ``EngineConfig.comm_events``.  With a comm stream the compute graph tells it a
+        bucket is final by bumping a per-bucket counter (a 1-lane kernel node,
+        system-scope release) that a bounded polling kernel on the comm stream waits
+        for.  Inline layout (no comm stream): the boundaries leave nothing in the graph."""
+        from ..parallel.comm import FlagSignal
         pool = torch.cuda.graph_pool_handle()
         nb = len(self.buckets)
-        self._multi = None
-        from ..parallel.comm import ExternalEvent, FlagSignal
-        sig = None
-        # the compute graph tells the comm stream a bucket is final by bumping a
-        # per-bucket counter (a 1-lane kernel node, system-scope release) that a
-        # bounded polling kernel on the comm stream waits for.  (External event-record
-        # nodes were measured too: the comm stream then started only after the whole
-        # compute graph, so the overlapped layouts overlapped nothing.)  Inline layout
-        # (no comm stream): events only mark the bucket boundaries.
-        if self.comm is not None:
-            sig = FlagSignal(nb, self.device)
-            evs = [sig.waiter(k) for k in range(nb)]
-        else:
-            evs = [ExternalEvent() for _ in range(nb)]
+        sig = FlagSignal(nb, self.device) if self.comm is not None else None
         gen = self._step_iter()
         g1, g2 = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
         with torch.cuda.graph(g1, pool=pool, capture_error_mode=CAPTURE_MODE):
@@ -1229,78 +1242,64 @@ class TrainEngine:
                 assert kind == "bucket", kind
                 if sig is not None:
                     sig.bump(k)
-                else:
-                    evs[k].record()
         with torch.cuda.graph(g2, pool=pool, capture_error_mode=CAPTURE_MODE):
             kind, _ = next(gen)
             assert kind == "done", kind
-        self._graphs = [g1, g2]
-        self._events = evs
-        self._signal = sig
-        if sig is not None:
-            self.handoff_order = "pre-issued" if self._preissue_ok() else "post-replay"
-        else:
-            self.handoff_order = "events" if self.comm is not None else "inline"
+        return [g1, g2], sig
 
-    def _capture_graphs(self, graph_comm: bool):
+    def _capture_single(self):
+        """The whole step as one graph, plus ``graph_steps`` = K > 1 steps as another."""
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, pool=torch.cuda.graph_pool_handle(), capture_error_mode=CAPTURE_MODE):
+            self._run_step()
+        multi = None
+        K = max(1, int(self.cfg.graph_steps))
+        if K > 1:  # K steps in one graph, own memory pool
+            gm = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(gm, pool=torch.cuda.graph_pool_handle(), capture_error_mode=CAPTURE_MODE):
+                for _ in range(K):
+                    self._run_step()
+            multi = (gm, K)
+        return [g], multi
+
+    def _capture_segments(self):
+        """One graph up to each bucket boundary and one for the optimizer."""
         pool = torch.cuda.graph_pool_handle()
-        graphs = []
-        self._multi = None
-        self._events = None
-        self._signal = None
         gen = self._step_iter()
-        nseg = len(self.buckets) + 1 if (self.segmented and not graph_comm) else 1
-        if nseg == 1:
+        graphs = []
+        for _ in range(len(self.buckets) + 1):
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, pool=pool, capture_error_mode=CAPTURE_MODE):
-                self._captured_step_body()
+                next(gen)
             graphs.append(g)
-            K = max(1, int(self.cfg.graph_steps))
-            if K > 1:  # K steps in one graph, own memory pool
-                gm = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(gm, pool=torch.cuda.graph_pool_handle(), capture_error_mode=CAPTURE_MODE):
-                    for _ in range(K):
-                        self._captured_step_body()
-                self._multi = (gm, K)
-        else:
-            for _ in range(nseg):
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, pool=pool, capture_error_mode=CAPTURE_MODE):
-                    next(gen)
-                graphs.append(g)
-        self._graphs = graphs
+        return graphs
 
     def _replay(self):
-        gs = self._graphs
-        if len(gs) == 1:
+        gs, nb = self._graphs, len(self.buckets)
+        if self._mode == SINGLE:
             gs[0].replay()
-            return
-        evs = getattr(self, "_events", None)
-        if evs is not None and len(gs) == 2:
-            sig = getattr(self, "_signal", None)
-            if sig is not None and self.handoff_order == "pre-issued":
-                # counters: the comm stream's waits + collectives can be queued BEFORE the
-                # compute graph (each waits for its own counter), so the comm queue holds
-                # them when the graph starts instead of receiving them behind it
+        elif self._mode == EVENT_SPLIT:
+            sig = self._signal
+            if sig is not None:
                 sig.expected += 1  # this replay's counter value
-                for k, ev in enumerate(evs):
-                    self._allreduce(k, after=ev)
+            # pre-issued: the comm stream's counter waits + collectives are queued BEFORE
+            # the compute graph (each waits for its own counter), so the comm queue holds
+            # them when the graph starts instead of receiving them behind it
+            pre = self.handoff_order == "pre-issued"
+            if not pre:
                 gs[0].replay()
-            else:
+            for k in range(nb):  # comm stream: behind the bucket's counter; inline: after gs[0]
+                self._allreduce(k, wait_counter=sig is not None)
+            if pre:
                 gs[0].replay()
-                if sig is not None:
-                    sig.expected += 1
-                for k, ev in enumerate(evs):  # comm stream: waits on the bucket's event; inline: after gs[0]
-                    self._allreduce(k, after=ev)
             self._join_comm()
             gs[1].replay()
-            return
-        nb = len(self.buckets)
-        for k in range(nb):
-            gs[k].replay()
-            self._allreduce(k)
-        self._join_comm()
-        gs[nb].replay()
+        else:
+            for k in range(nb):
+                gs[k].replay()
+                self._allreduce(k)
+            self._join_comm()
+            gs[nb].replay()
 
     def train_steps(self, n: int, materialize: bool = True):
         """Run ``n`` optimizer steps (``batch_fn`` draws each step's batch on the device).
@@ -1311,7 +1310,7 @@ class TrainEngine:
         Returns the device loss tensor of the last step (no host sync)."""
         done = 0
         while done < n:
-            multi = getattr(self, "_multi", None)
+            multi = self._multi
             if multi is not None and n - done >= multi[1]:
                 multi[0].replay()
                 self.steps_done += multi[1]
@@ -1349,7 +1348,7 @@ class TrainEngine:
         if use_graph and self._graphs is not None:
             self._replay()
         else:
-            self._run_eager()
+            self._run_step()
             self._eager_steps += 1
         self.steps_done += 1
         self._lazy_dirty = True
@@ -1416,7 +1415,7 @@ class TrainEngine:
         snapshot before taking the next."""
         self.materialize_lazy()
         cur = torch.cuda.current_stream(self.device) if self.is_cuda else None
-        if getattr(self, "_snap", None) is None:
+        if self._snap is None:
             pin = self.is_cuda
             host = [torch.empty(t.shape, dtype=t.dtype, pin_memory=pin)
                     for t in (self.flat_p, self.flat_m, self.flat_v, self.step_ctr, self.rng)]
@@ -1470,16 +1469,14 @@ class TrainEngine:
                           "select; updating them every step (lazy weight decay off)")
             self.materialize_lazy()
             self.lazy = None
-            self._graphs = None
-            self._multi = None
-            self._eager_steps = 0
+            self._drop_capture(rewarm=True)
 
     def scheduler_state_dict(self, sched_step: Optional[int] = None) -> dict:
         """torch CosineAnnealingLR-format state dict (at ``sched_step``, default: now).
         The key layout comes from a real scheduler built once and cached (building a
         torch optimizer costs ~1.5 s the first time in a process -- it imports the
         compiler stack -- which must not land in a background checkpoint write)."""
-        if getattr(self, "_sched_template", None) is None:
+        if self._sched_template is None:
             opt = torch.optim.AdamW([torch.zeros(1, requires_grad=True)], lr=self.cfg.lr)
             sch = torch.optim.lr_scheduler.CosineAnnealingLR(opt, max(self.cfg.t_max, 1), self.cfg.eta_min)
             self._sched_template = sch.state_dict()

@@ -9,7 +9,9 @@ on the concatenated batch (multi_gpu_trainer.py:88,128: DDP's bucketed all-reduc
 overlapped with backward).
 
 Covered: the event-split pre-issued layout (overlap-2, comm stream ahead of the
-compute replay) and the captured inline layout with 4-step graphs (graph-inline-1).
+compute replay), the event-split inline layout (inline-1: one host-issued all-reduce on
+the compute stream between the step's two graphs) and the captured inline layout with
+4-step graphs (graph-inline-1).
 Not covered: the captured comm-BRANCH layout (graph-overlap-*, not an autotune
 candidate): in one process its graph branches run on runtime-internal streams that
 can share a hardware queue with the other engine's graph, and the loopback
@@ -45,7 +47,7 @@ def _engine(dp: bool, K: int = 1):
     return TrainEngine(model, cfg)
 
 
-@pytest.mark.parametrize("layout,K", [("overlap-2", 1), ("graph-inline-1", 4)])
+@pytest.mark.parametrize("layout,K", [("overlap-2", 1), ("inline-1", 1), ("graph-inline-1", 4)])
 def test_two_engines_cross_queue_handoff(layout, K, monkeypatch):
     monkeypatch.setenv("DDIM_COLD_HANDOFF_TIMEOUT_US", str(TIMEOUT_US))
     x, y, t = _batch(2 * B)
@@ -82,6 +84,8 @@ def test_two_engines_cross_queue_handoff(layout, K, monkeypatch):
     assert not any(eng.comm_error() for eng in engs), f"hand-off wait timed out ({layout})"
     if layout == "overlap-2":
         assert all(eng.handoff_order == "pre-issued" for eng in engs), [eng.handoff_order for eng in engs]
+    elif layout == "inline-1":
+        assert all(eng.handoff_order == "inline" and len(eng._graphs) == 2 for eng in engs)
     else:
         assert all(len(eng._graphs) == 1 and eng._multi is not None for eng in engs)
     assert torch.equal(engs[0].flat_p, engs[1].flat_p), "replicas diverged"

@@ -86,7 +86,7 @@ if __name__ == "__main__":
     natb, loss4, failed4, ng4 = run("captured", comm="native", wire="bf16")
     gref, gl0, _, _ = run(None, gauss=True)
     gcap, gl1, gfailed, gng = run("captured", gauss=True)
-    # compute graphs split at external events, collectives host-issued on the comm stream
+    # event-split: forward + backward graph, optimizer graph, collectives host-issued on the comm stream
     ev, loss5, _, ng5 = run("events")
     evn, loss6, _, ng6 = run("events", comm="native")
     gev, gl2, _, gng2 = run("events", gauss=True)
