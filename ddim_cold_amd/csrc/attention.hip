@@ -159,7 +159,10 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const bf16* __restrict__ 
         if (thr) {
           const int key = kv0 + 16 * t + 4 * g + r;
           const uint32_t idx = (uint32_t)(((size_t)bh * N + q) * attn_mask_ld(N) + key);
-          pv = dropout_keep(salt, idx, thr) ? pv * dsc : 0.f;
+          // the keep scale 1/(1-p) goes into the final 1/l: scaled here, the row max's
+          // p = 1 became bf16(1/(1-p)) in every row (1.109 for 1.111 at p = 0.1), a scale
+          // error of -4e-4 to -6e-4 on o (profiles/attn_error.txt)
+          pv = dropout_keep(salt, idx, thr) ? pv : 0.f;
         }
         st[t][r] = pv;
       }
@@ -177,7 +180,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const bf16* __restrict__ 
     }
   }
   if (q < N) {
-    const float inv = 1.f / l_run;
+    const float inv = dsc / l_run;  // dsc = 1 without dropout
     const int D = H * HD;
     bf16* orow = out + ((size_t)b * N + q) * D + h * HD;
 #pragma unroll

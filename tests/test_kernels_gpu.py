@@ -13,6 +13,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from ddim_cold_amd import ops
+from ddim_cold_amd.ops import check
 from ddim_cold_amd.ops import reference as ref
 
 DEV = "cuda"
@@ -444,6 +445,29 @@ def test_linear_wgrad_multi_sqnorm_partials(store, lazy, big):
 
 
 # ------------------------------------------------------------------ attention
+def attn_within(qkv, do, o, lse, o_mirror, dqkv, dqkv_mirror, scale, r, p, tag, bh0=0):
+    """The kernel's ``o``, ``lse`` and ``dq`` / ``dk`` / ``dv`` (each on its own) against the
+    fp64 truth, bounded by what the mirror reference achieves at the same inputs
+    (:mod:`ddim_cold_amd.ops.check`).  ``dqkv`` None: forward only."""
+    _, B, H, N, hd = qkv.shape
+    truth = check.attn_truth(qkv, do if dqkv is not None else None, scale, r, 5, p, bh0)
+    check.assert_lse(lse, truth[1], f"{tag} lse")
+    check.assert_within(check.split_o(o, B, H, N, hd), check.split_o(o_mirror, B, H, N, hd), truth[0], f"{tag} o")
+    if dqkv is None:
+        return
+    # N = 1: dp == delta, so dQ and dK are zero in exact arithmetic and what comes out is the
+    # fp32 cancellation residue of two hd-term dot products (<= hd 2^-24 sum|dO_c V_c| each),
+    # times |K| or |Q| and the softmax scale: no signal to be relative to
+    floor = 0.0
+    if N == 1:
+        dof = check.split_o(do, B, H, N, hd).float()
+        floor = (hd * 2.0 ** -24 * (dof * qkv[2].float()).abs().sum(-1).max().item()
+                 * qkv[:2].float().abs().max().item() * scale)
+    got, mir = check.split_dqkv(dqkv, B, H, N, hd), check.split_dqkv(dqkv_mirror, B, H, N, hd)
+    for i, n in enumerate(("dq", "dk", "dv")):
+        check.assert_within(got[i], mir[i], truth[2 + i], f"{tag} {n}", floor=floor if i < 2 else 0.0)
+
+
 @pytest.mark.parametrize("B,H,N,hd,p", [(4, 12, 65, 32, 0.0), (4, 12, 65, 32, 0.1), (2, 4, 257, 64, 0.1),
                                         (1, 2, 17, 32, 0.0), (1, 6, 626, 64, 0.0), (2, 3, 130, 64, 0.2),
                                         # short-sequence path (N <= 128): every padded size, both head dims
@@ -466,6 +490,7 @@ def test_attention_fwd_bwd(B, H, N, hd, p):
     dqr = ref.attn_bwd(do, qkv, o, lse, scale, r, 5, p)
     assert dq.shape == (B * N, 3 * H * hd)
     close(dq, dqr, 3e-2, 3e-2, "dqkv")
+    attn_within(qkv, do, o, lse, or_, dq, dqr, scale, r, p, f"fwd_bwd B{B} H{H} N{N} hd{hd} p{p}")
     # keep flags stored by the forward == masks re-hashed in the backward, bit for bit
     keep = ops.attn_keep_buffer(qkv, p)
     if keep is not None:
@@ -490,7 +515,9 @@ def test_attention_n2501(p):
     close(o, or_, 2e-2, 2e-2, "o")
     do = bf(B, N, H * hd)
     dq = ops.attn_bwd(do, qkv, o, lse, scale, r, 5, p, keep=keep)
-    close(dq, ref.attn_bwd(do, qkv, o, lse, scale, r, 5, p), 3e-2, 3e-2, "dqkv")
+    dqr = ref.attn_bwd(do, qkv, o, lse, scale, r, 5, p)
+    close(dq, dqr, 3e-2, 3e-2, "dqkv")
+    attn_within(qkv, do, o, lse, or_, dq, dqr, scale, r, p, f"n2501 p{p}")
     if keep is not None:  # stored words == re-hashed masks, bit for bit
         assert torch.equal(ops.attn_bwd(do, qkv, o, lse, scale, r, 5, p), dq)
 
@@ -518,6 +545,8 @@ def test_attention_mask_index_beyond_2p31():
                        scale, r, 5, p, bh0=H - 1)
     dqv = dq.view(B * N, 3, D)[:, :, D - hd:].reshape(B * N, 3 * hd)
     close(dqv, dqr, 3e-2, 3e-2, "dqkv (last head)")
+    attn_within(last, do[:, :, D - hd:].contiguous(), o[:, :, D - hd:].contiguous(), lse[:, H - 1:], or_, dqv, dqr,
+                scale, r, p, "mask index > 2^31, last head", bh0=H - 1)
     assert torch.equal(ops.attn_bwd(do, qkv, o, lse, scale, r, 5, p), dq)
 
 
@@ -567,8 +596,146 @@ def test_attention_lazy_max_ramp(B, H, N, hd, p):
     close(lse, lser, 1e-3, 1e-4, "lse")
     close(o, or_, 2e-2, 2e-2, "o")
     do = bf(B, N, H * hd)
-    close(ops.attn_bwd(do, qkv, o, lse, scale, r, 5, p), ref.attn_bwd(do, qkv, o, lse, scale, r, 5, p),
-          3e-2, 3e-2, "dqkv")
+    dq, dqr = ops.attn_bwd(do, qkv, o, lse, scale, r, 5, p), ref.attn_bwd(do, qkv, o, lse, scale, r, 5, p)
+    close(dq, dqr, 3e-2, 3e-2, "dqkv")
+    attn_within(qkv, do, o, lse, or_, dq, dqr, scale, r, p, f"lazy-max ramp B{B} H{H} N{N} hd{hd} p{p}")
+
+
+def _hd_alt(ns, both=()):
+    """(N, hd): hd = 32 at the even entries of ``ns``, 64 at the odd ones, both at ``both``."""
+    return [(n, hd) for i, n in enumerate(ns) for hd in ((32, 64) if n in both else ((32, 64)[i % 2],))]
+
+
+ATTN_EDGES = (
+    # short path (N <= 128): every padded size's first and last N, both head dims
+    [("short", 2, 3, n, hd) for n in (1, 16, 31, 32, 96, 127, 128) for hd in (32, 64)]
+    # v1 forward (few heads, 128 < N < 384) + the dQ / dK-dV kernels with re-hashed masks
+    + [("v1", 2, 2, n, hd) for n, hd in _hd_alt((129, 192, 321, 383))]
+    # resident-KV forward (N <= 320, B*H >= 192) + the backward kernels with stored masks
+    + [("resident", 48, 4, n, hd) for n, hd in _hd_alt((129, 192, 256, 319, 320))]
+    # flash v2: first N, one-key tail tile, empty second half of the last workgroup, whole tiles
+    + [("flash2", 1, 2, n, hd) for n, hd in _hd_alt((384, 385, 448, 512, 640), both=(384, 385))]
+    + [("flash2", 3, 1, 577, 32)])  # three (b, h) groups through xcd_remap with one head
+
+
+@pytest.mark.parametrize("p", [0.0, 0.1])
+@pytest.mark.parametrize("path,B,H,N,hd", ATTN_EDGES)
+def test_attention_tile_edges(path, B, H, N, hd, p):
+    """Sequence lengths at the dispatch boundaries and tile edges of every attention path:
+    whole numbers of 64-key tiles (the unmasked loop alone), one-key tails, N where the
+    mask row stride is not N (129, 385), the first and last N of each kernel.  Forward
+    and backward against the fp64 truth, with re-hashed and with stored dropout masks."""
+    assert {"short": N <= 128, "v1": 128 < N < 384 and B * H < 192, "resident": 128 < N <= 320 and B * H >= 192,
+            "flash2": N >= 384}[path]
+    qkv = bf(3, B, H, N, hd)
+    do = bf(B, N, H * hd)
+    r = rng()
+    scale = hd ** -0.5
+    tag = f"edge {path} B{B} H{H} N{N} hd{hd} p{p}"
+    o, lse = ops.attn_fwd(qkv, scale, r, 5, p)
+    or_, _ = ref.attn_fwd(qkv, scale, r, 5, p)
+    dq = ops.attn_bwd(do, qkv, o, lse, scale, r, 5, p)
+    dqr = ref.attn_bwd(do, qkv, o, lse, scale, r, 5, p)
+    attn_within(qkv, do, o, lse, or_, dq, dqr, scale, r, p, tag)
+    keep = ops.attn_keep_buffer(qkv, p)
+    assert (keep is not None) == (p > 0 and path != "v1")
+    if keep is not None:  # stored keep words: the same bits, so the same outputs
+        o2, lse2 = ops.attn_fwd(qkv, scale, r, 5, p, keep_out=keep)
+        assert torch.equal(o2, o) and torch.equal(lse2, lse), "forward storing keep words"
+        assert torch.equal(ops.attn_bwd(do, qkv, o, lse, scale, r, 5, p, keep=keep), dq), "backward from keep words"
+
+
+# one N per kernel path: short, v1, resident, flash v2, flash v2 at the benchmark length
+ATTN_PROBES = [(2, 2, 97, 32), (1, 4, 257, 64), (48, 4, 257, 32), (1, 2, 448, 64), (1, 2, 2501, 64)]
+BF16_U = 2.0 ** -8  # one rounding to bf16 (8 significand bits)
+
+
+@pytest.mark.parametrize("p", [0.0, 0.1])
+@pytest.mark.parametrize("B,H,N,hd", ATTN_PROBES)
+def test_attention_uniform_probe(B, H, N, hd, p):
+    """q = 0, V = 1: every probability is 1/N whatever K is.  lse = log N to 8 fp32 ulps;
+    without dropout o = 1 exactly (N ones over a row sum of N); with it o = kept / (N (1-p))
+    from the kept counts of the reference mask, to the one bf16 rounding of the output
+    (every forward sums exact ones and folds 1/(1-p) into the final 1/l; the expected
+    value is taken in fp64, a bf16 constant in it would add a rounding of its own).
+    A wrong rescale is 10 %, a pad key or a missed key log(N+-1) in lse."""
+    qkv = bf(3, B, H, N, hd)
+    qkv[0] = 0
+    qkv[2] = 1
+    r = rng()
+    o, lse = ops.attn_fwd(qkv, 0.37, r, 5, p)
+    err = (lse.double() - math.log(N)).abs().max().item()
+    assert err <= 8 * 2.0 ** -23 * math.log(N), f"lse: {err:.3e}"
+    o = check.split_o(o, B, H, N, hd).double()
+    if p == 0:
+        assert torch.equal(o, torch.ones_like(o))
+        return
+    kept = ref.attn_keep_mask(B, H, N, r, 5, p, DEV).sum(-1, keepdim=True).double()
+    want = (kept / (N * (1.0 - p))).expand_as(o)
+    rel = ((o - want).abs() / want).max().item()
+    assert rel <= BF16_U, f"o vs kept / (N (1-p)): {rel:.3e}"
+
+
+def _sweep_positions(N):
+    return sorted({0, 63, 64, (N - 1) // 64 * 64, N - 2, N - 1})
+
+
+@pytest.mark.parametrize("B,H,N,hd", ATTN_PROBES)
+def test_attention_key_position_probe(B, H, N, hd):
+    """One key j leads every row by more than 40 in score (K[j] = 12 u, q = u, |u|^2 = hd,
+    the rest 0.05 noise), so P is one-hot to e^-40: o[i] = V[j] exactly, dV[j] = sum_i dO_i
+    to one bf16 rounding (plus the fp32 sum's own N 2^-24 max|dO|), every other dV row
+    <= 1e-6.  j over both ends, the tile edges and the ragged tail: a dropped or
+    duplicated key is an O(1) error."""
+    g = torch.Generator(device=DEV).manual_seed(11)
+    u = torch.randn(hd, device=DEV, generator=g)
+    u = u / u.norm() * math.sqrt(hd)
+    r = rng()
+    scale = hd ** -0.5
+    do = bf(B, N, H * hd)
+    dsum = check.split_o(do, B, H, N, hd).double().sum(2)  # [B,H,hd]
+    slack = N * 2.0 ** -24 * do.float().abs().max().item()
+    for j in _sweep_positions(N):
+        qkv = torch.empty(3, B, H, N, hd, device=DEV)
+        qkv[0] = u
+        qkv[1] = 0.05 * torch.randn(B, H, N, hd, device=DEV, generator=g)
+        qkv[1, :, :, j] = 12.0 * u
+        qkv[2] = torch.randn(B, H, N, hd, device=DEV, generator=g)
+        qkv = qkv.to(torch.bfloat16)
+        o_tok, lse = ops.attn_fwd(qkv, scale, r, 5, 0.0)
+        o = check.split_o(o_tok, B, H, N, hd)
+        assert torch.equal(o, qkv[2, :, :, j:j + 1].expand_as(o)), f"o != V[{j}]"
+        dv = check.split_dqkv(ops.attn_bwd(do, qkv, o_tok, lse, scale, r, 5, 0.0), B, H, N, hd)[2].double()
+        e = (dv[:, :, j] - dsum).abs() - BF16_U * dsum.abs()
+        assert e.max().item() <= slack, f"dV[{j}] vs sum dO: {e.max().item():.3e} over one bf16 rounding"
+        dv[:, :, j] = 0
+        assert dv.abs().max().item() <= 1e-6, f"dV rows other than {j}: {dv.abs().max().item():.3e}"
+
+
+@pytest.mark.parametrize("B,H,N,hd", ATTN_PROBES)
+def test_attention_query_position_probe(B, H, N, hd):
+    """The same sweep over the query position, for dQ: dO has one non-zero row i, so dS --
+    and with it dQ -- is exactly zero in every other row, and row i (with the rank-one
+    dK and dV it feeds) is held to the fp64 truth.  (With the one-hot P of the key sweep
+    dQ would vanish identically, dp = delta; here q, k, v are unit normal.)"""
+    qkv = bf(3, B, H, N, hd)
+    r = rng()
+    scale = hd ** -0.5
+    o, lse = ops.attn_fwd(qkv, scale, r, 5, 0.0)
+    for i in _sweep_positions(N):
+        do = torch.zeros(B, N, H * hd, dtype=torch.bfloat16, device=DEV)
+        do[:, i] = bf(B, H * hd)
+        dqkv = ops.attn_bwd(do, qkv, o, lse, scale, r, 5, 0.0)
+        got = check.split_dqkv(dqkv, B, H, N, hd)
+        mir = check.split_dqkv(ref.attn_bwd(do, qkv, o, lse, scale, r, 5, 0.0), B, H, N, hd)
+        truth = check.attn_truth(qkv, do, scale, r, 5, 0.0)[2:]
+        rest = got[0].clone()
+        rest[:, :, i] = 0
+        assert not rest.any(), f"dQ rows other than {i} are not zero: max {rest.float().abs().max().item():.3e}"
+        tag = f"dO row {i} B{B} H{H} N{N} hd{hd}"
+        check.assert_within(got[0][:, :, i], mir[0][:, :, i], truth[0][:, :, i], f"{tag} dq[{i}]")
+        check.assert_within(got[1], mir[1], truth[1], f"{tag} dk")
+        check.assert_within(got[2], mir[2], truth[2], f"{tag} dv")
 
 
 # ------------------------------------------------------------------ embedding / loss
