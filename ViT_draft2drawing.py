@@ -8,6 +8,12 @@ image to t_start in 1599..1999 (step 50), denoise each with DDIM k=10 and
 write the 1 x 10 grid ``draft2img.png``.  Here the 9 noise levels run as one
 batched, hipGraph-captured img2img call.  Without the draft / checkpoint
 files (not shipped) a synthetic draft / random init is used, with a warning.
+
+``--predict x0`` samples a model trained to predict the clean image (``dataset:
+cold_x0``) with the Cold Diffusion update (``--algorithm`` 1 or 2).  ``--restore
+IMAGE`` replaces the draft -> drawing stage: IMAGE is pixelated at every level
+1..S and each version restored (x0 models: one batched call; prev models: one
+call per level); ``restore.png`` shows the pixelated inputs over the results.
 """
 import argparse
 import os
@@ -29,6 +35,12 @@ def main(argv=None):
     ap.add_argument("--out_dir", default=os.path.join(HERE, "Saved_Models"))
     ap.add_argument("--k", type=int, default=10)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--predict", choices=("prev", "x0"), default="prev",
+                    help="what the cold model predicts: x_{t-1} (dataset: cold) or x0 (dataset: cold_x0)")
+    ap.add_argument("--algorithm", type=int, choices=(1, 2), default=2,
+                    help="cold x0 update: 1 = D(x0, t-1), 2 = x_t - D(x0, t) + D(x0, t-1)")
+    ap.add_argument("--restore", metavar="IMAGE", default=None,
+                    help="restore IMAGE from each pixelation level instead of the draft -> drawing stage")
     a = ap.parse_args(argv)
     from ddim_cold_amd.data.datasets import load_image
     from ddim_cold_amd.data.synthetic import synthetic_pool
@@ -44,8 +56,27 @@ def main(argv=None):
         print(f"warning: {a.ckpt} not found, using random-init weights", file=sys.stderr)
     model.to(device).eval()
     g = torch.Generator().manual_seed(a.seed)
-    seq = model.cold_diffusion_sequence(device, N=5, generator=g)
+    seq = model.cold_diffusion_sequence(device, N=5, generator=g, predict=a.predict, algorithm=a.algorithm)
     p1 = save_sequence_grid(seq, get_next_path(os.path.join(a.out_dir, "denoise_sequence.png")))
+    if a.restore is not None:
+        from ddim_cold_amd.diffusion.schedule import cold_steps
+        from ddim_cold_amd.ops.reference import pixelate
+        if os.path.isfile(a.restore):
+            img = load_image(a.restore, model.img_size)
+        else:
+            print(f"warning: {a.restore} not found, using a synthetic picture", file=sys.stderr)
+            img = synthetic_pool(1, tuple(model.img_size), seed=a.seed)[0]
+        levels = list(range(1, cold_steps(model.img_size[1]) + 1))
+        imgs = img.unsqueeze(0).expand(len(levels), -1, -1, -1)
+        if a.predict == "x0":  # every level in one batch, each joining the grid at its own step
+            out = model.cold_restore(imgs, levels, device, predict="x0", algorithm=a.algorithm)
+        else:
+            out = torch.cat([model.cold_restore(imgs[i:i + 1], v, device) for i, v in enumerate(levels)])
+        pix = torch.cat([pixelate(imgs[i:i + 1], 2 ** v) for i, v in enumerate(levels)])
+        p2 = save_grid(torch.cat([(pix + 1) / 2, out]), get_next_path(os.path.join(a.out_dir, "restore.png")),
+                       nrow=len(levels))
+        print(f"wrote {p1} and {p2}")
+        return 0
     if os.path.isfile(a.draft):
         draft = load_image(a.draft, model.img_size)
     else:

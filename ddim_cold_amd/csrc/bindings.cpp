@@ -1085,6 +1085,54 @@ void ddim_step_(Tensor x, Tensor x0_raw, Tensor x0_out, Tensor coef) {
                    coef.data_ptr<float>(), x.numel(), cur_stream());
 }
 
+// Cold-diffusion sampling step of an x0-predicting model (csrc/diffusion.hip
+// cold_step_kernel), in place on x; every check before the launch.
+static void cold_step_impl(Tensor& x, const Tensor& x0, const Tensor& t, int64_t B, int64_t C, int64_t H, int64_t W,
+                           int64_t patch, int64_t algorithm, const c10::optional<Tensor>& patches_out, bool rows) {
+  CHECK_IN(x, F32); CHECK_IN(x0, F32); CHECK_IN(t, I64);
+  const c10::DeviceGuard guard(x.device());
+  TORCH_CHECK(x0.device() == x.device() && t.device() == x.device(), "cold_step: x, x0 and t on one device");
+  TORCH_CHECK(B >= 1 && C >= 1 && H >= 1 && W >= 1 && patch >= 0, "cold_step: sizes");
+  const int64_t n = B * C * H * W;
+  TORCH_CHECK(x.numel() == n && x0.sizes() == x.sizes() && t.numel() == B, "cold_step shapes");
+  TORCH_CHECK(n < ((int64_t)1 << 31), "cold_step: 32-bit indexing needs fewer than 2^31 elements");
+  TORCH_CHECK(algorithm == 1 || algorithm == 2, "cold_step: algorithm 1 (naive) or 2 (improved)");
+  const char *xp = (const char*)x.data_ptr(), *sp = (const char*)x0.data_ptr();
+  TORCH_CHECK(xp + n * 4 <= sp || sp + n * 4 <= xp, "cold_step: x and x0 must not alias");
+  TORCH_CHECK((uintptr_t)xp % 16 == 0, "cold_step: x must be 16-byte aligned");
+  const bool have_out = patches_out.has_value() && patches_out->defined();
+  if (rows || have_out) {
+    TORCH_CHECK(patch >= 1 && H % patch == 0 && W % patch == 0, "cold_step: image size must be divisible by patch");
+    TORCH_CHECK((C * patch * patch) % 4 == 0, "cold_step: C*p*p must be a multiple of 4");
+  } else {
+    TORCH_CHECK((C * H * W) % 4 == 0, "cold_step: C*H*W must be a multiple of 4");
+  }
+  void* po = nullptr;
+  if (have_out) {
+    CHECK_IN((*patches_out), BF16);
+    const int64_t F = C * patch * patch;
+    TORCH_CHECK(patches_out->device() == x.device() && patches_out->dim() == 2 && patches_out->size(1) == F &&
+                    patches_out->size(0) == n / F, "cold_step: patches_out must be [B*P, C*p*p]");
+    po = patches_out->data_ptr();
+    TORCH_CHECK((uintptr_t)po % 8 == 0, "cold_step: patches_out must be 8-byte aligned");
+  }
+  cold_step_launch(x.data_ptr<float>(), x0.data_ptr<float>(), t.data_ptr<int64_t>(), po, B, C, H, W,
+                   have_out || rows ? patch : 0, algorithm, rows, cur_stream());
+}
+
+// image layout: x / x0 [B,C,H,W]; patches_out (optional) conv-im2col rows for `patch`
+void cold_step_(Tensor x, Tensor x0, Tensor t, int64_t algorithm, int64_t patch, c10::optional<Tensor> patches_out) {
+  TORCH_CHECK(x.dim() == 4, "cold_step_: x must be [B,C,H,W]");
+  cold_step_impl(x, x0, t, x.size(0), x.size(1), x.size(2), x.size(3), patch, algorithm, patches_out, false);
+}
+
+// patch-row layout: x / x0 / patches_out [B*P, C*p*p] in the head's output column order
+void cold_step_rows_(Tensor x, Tensor x0, Tensor t, int64_t batch, int64_t C, int64_t H, int64_t W, int64_t patch,
+                     int64_t algorithm, c10::optional<Tensor> patches_out) {
+  TORCH_CHECK(patch >= 1 && x.dim() == 2 && x.size(1) == C * patch * patch, "cold_step_rows_: x must be [B*P, C*p*p]");
+  cold_step_impl(x, x0, t, batch, C, H, W, patch, algorithm, patches_out, true);
+}
+
 void randn_(Tensor out, Tensor rng, int64_t site) {
   CHECK_IN(out, F32); check_rng(rng);
   const c10::DeviceGuard guard(out.device());
@@ -1277,6 +1325,9 @@ TORCH_LIBRARY(ddim_cold, m) {
   m.def("advance_counters(Tensor(a!) step, Tensor(b!) rng, Tensor? sq) -> ()");
   m.def("ddim_step(Tensor x_t, Tensor x0_raw, Tensor coef) -> (Tensor, Tensor)");
   m.def("ddim_step_(Tensor(a!) x, Tensor x0_raw, Tensor(b!) x0_out, Tensor coef) -> ()");
+  m.def("cold_step_(Tensor(a!) x, Tensor x0, Tensor t, int algorithm, int patch, Tensor(b!)? patches_out) -> ()");
+  m.def("cold_step_rows_(Tensor(a!) x, Tensor x0, Tensor t, int batch, int C, int H, int W, int patch, "
+        "int algorithm, Tensor(b!)? patches_out) -> ()");
   m.def("randn_(Tensor(a!) out, Tensor rng, int site) -> ()");
   m.def("q_sample(Tensor x0, Tensor t, Tensor eps, int total_steps) -> Tensor");
   m.def("pixelate_pair(Tensor img, Tensor? idx, Tensor t, int B) -> (Tensor, Tensor)");
@@ -1324,6 +1375,8 @@ TORCH_LIBRARY_IMPL(ddim_cold, CUDA, m) {
   m.impl("advance_counters", &advance_counters);
   m.impl("ddim_step", &ddim_step);
   m.impl("ddim_step_", &ddim_step_);
+  m.impl("cold_step_", &cold_step_);
+  m.impl("cold_step_rows_", &cold_step_rows_);
   m.impl("randn_", &randn_);
   m.impl("q_sample", &q_sample);
   m.impl("pixelate_pair", &pixelate_pair);

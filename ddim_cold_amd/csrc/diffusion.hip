@@ -150,6 +150,78 @@ __global__ __launch_bounds__(256) void gauss_batch_kernel(const float* __restric
   }
 }
 
+// Cold-diffusion sampling step for an x0-predicting model (Bansal et al. 2022), in
+// place on x, with x0 the clamped prediction and D(., t) = the training degradation
+// (pix_src for factor 2^t):
+//   algorithm 1: x <- D(x0, t-1)                 algorithm 2: x <- (x - D(x0, t)) + D(x0, t-1)
+// Per-sample t from the device; a sample with t <= 0 is skipped (no load, no store).
+// ROWS = false: x / x0 are [B,C,H,W]; pout (optional) gets the new x as bf16
+// conv-im2col patch rows [B*P][C*p*p] (column c*p*p + a*p + b), p = patch (0: no pout).
+// ROWS = true: x / x0 / pout are [B*P][F] patch rows in the head's output column order
+// (column (a*p + b)*C + c): element -> pixel (y, x, c) -> the two source pixels ->
+// their (row, column) in x0 (other rows once the block outgrows the patch).
+// Each thread owns 4 consecutive elements (one sample: C*H*W % 4 == 0): a 16-byte
+// load and store of x, scalar gathers from x0, an 8-byte bf16 store.
+template <bool ROWS>
+__global__ __launch_bounds__(256) void cold_step_kernel(float* __restrict__ x, const float* __restrict__ x0,
+                                                        const int64_t* __restrict__ t, bf16* __restrict__ pout,
+                                                        int B, int C, int H, int W, int p, int alg) {
+  const int per = C * H * W, n4 = B * (per / 4);
+  const int Wp = p > 0 ? W / p : 0, F = C * p * p;
+  for (int q = blockIdx.x * 256 + threadIdx.x; q < n4; q += gridDim.x * 256) {
+    const int e = 4 * q, b = e / per, rem0 = e - b * per;
+    const int64_t tb = t[b];
+    if (tb <= 0) continue;
+    const int tt = tb < 30 ? (int)tb : 30;  // (2^t beyond the image: one block, as pix_src clamps)
+    const int f1 = 1 << tt, f0 = 1 << (tt - 1);
+    const float* s = x0 + (size_t)b * per;
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (alg == 2) v = *reinterpret_cast<const f32x4*>(x + e);
+    int po[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int rem = rem0 + j;
+      int c, yy, xx;
+      if (ROWS) {
+        const int row = rem / F, col = rem - row * F, ab = col / C, a = ab / p;
+        c = col - ab * C;
+        yy = (row / Wp) * p + a;
+        xx = (row % Wp) * p + (ab - a * p);
+      } else {
+        const int r = rem / W;
+        xx = rem - r * W;
+        c = r / H;
+        yy = r - c * H;
+      }
+      const int y1 = pix_src(yy, H, f1), x1 = pix_src(xx, W, f1);
+      const int y0 = pix_src(yy, H, f0), x0s = pix_src(xx, W, f0);
+      float a1, a0;
+      if (ROWS) {
+        a1 = s[((y1 / p) * Wp + x1 / p) * F + ((y1 % p) * p + x1 % p) * C + c];
+        a0 = s[((y0 / p) * Wp + x0s / p) * F + ((y0 % p) * p + x0s % p) * C + c];
+        po[j] = rem;
+      } else {
+        a1 = s[(c * H + y1) * W + x1];
+        a0 = s[(c * H + y0) * W + x0s];
+        po[j] = p > 0 ? ((yy / p) * Wp + xx / p) * F + c * p * p + (yy % p) * p + xx % p : 0;
+      }
+      v[j] = alg == 2 ? (v[j] - a1) + a0 : a0;
+    }
+    *reinterpret_cast<f32x4*>(x + e) = v;
+    if (pout != nullptr) {
+      bf16* o = pout + (size_t)b * per;
+      if (ROWS || p % 4 == 0) {  // 4 consecutive pixels of one patch line: consecutive columns
+        bf16x4 h;
+        h[0] = f2bf(v[0]); h[1] = f2bf(v[1]); h[2] = f2bf(v[2]); h[3] = f2bf(v[3]);
+        *reinterpret_cast<bf16x4*>(o + po[0]) = h;
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[po[j]] = f2bf(v[j]);
+      }
+    }
+  }
+}
+
 static int g_grid(int64_t n) {
   int64_t g = (n + 255) / 256;
   if (g > 4096) g = 4096;
@@ -164,6 +236,17 @@ using namespace dc;
 void ddim_step_launch(const float* x_t, const float* x0_raw, float* x_next, float* x0_out, const float* coef,
                       int64_t n, hipStream_t stream) {
   hipLaunchKernelGGL(ddim_step_kernel, dim3(g_grid(n)), dim3(256), 0, stream, x_t, x0_raw, x_next, x0_out, coef, n);
+}
+
+void cold_step_launch(float* x, const float* x0, const int64_t* t, void* patches_out, int B, int C, int H, int W,
+                      int patch, int algorithm, bool rows, hipStream_t stream) {
+  const dim3 grid(g_grid((int64_t)B * C * H * W / 4));
+  bf16* po = reinterpret_cast<bf16*>(patches_out);
+  if (rows)
+    hipLaunchKernelGGL(cold_step_kernel<true>, grid, dim3(256), 0, stream, x, x0, t, po, B, C, H, W, patch, algorithm);
+  else
+    hipLaunchKernelGGL(cold_step_kernel<false>, grid, dim3(256), 0, stream, x, x0, t, po, B, C, H, W, patch,
+                       algorithm);
 }
 
 void randn_launch(float* out, int64_t n, const int64_t* rng, int site, hipStream_t stream) {

@@ -279,6 +279,12 @@ void ddim_step_launch(const float* x_t, const float* x0_raw, float* x_next, floa
                       int64_t n, hipStream_t stream);
 void pixelate_pair_launch(const float* img, const int64_t* idx, const int64_t* t, float* x_t, float* x_tm1,
                           int B, int C, int H, int W, hipStream_t stream);
+// Cold-diffusion sampling step of an x0-predicting model, in place on x (algorithm 1 / 2
+// of Bansal et al. 2022; per-sample t, t <= 0 skipped).  rows: x / x0 / patches_out are
+// patch rows [B*P][C*p*p] in the head's output order; otherwise [B,C,H,W] images and
+// patches_out (optional, bf16) conv-im2col patch rows (patch 0: none).  B*C*H*W < 2^31.
+void cold_step_launch(float* x, const float* x0, const int64_t* t, void* patches_out, int B, int C, int H, int W,
+                      int patch, int algorithm, bool rows, hipStream_t stream);
 void randn_launch(float* out, int64_t n, const int64_t* rng, int site, hipStream_t stream);
 void q_sample_launch(const float* x0, const int64_t* t, const float* eps, float* out, int B, int64_t per,
                      int total_steps, hipStream_t stream);

@@ -18,7 +18,9 @@ Sampling always runs the denoiser in eval mode (no dropout); the reference's
 
 Every step is ONE forward whose head-GEMM epilogue applies the step (DDIM
 update, cold clamp, or img2img's DDIM update with per-sample coefficients) and
-hands the next step its bf16 patch rows.  (Splitting a batch into concurrent
+hands the next step its bf16 patch rows; the cold sampler of an x0-predicting model
+(``ColdSampler(predict="x0")``) instead follows each forward with one
+:func:`ops.cold_step_` launch.  (Splitting a batch into concurrent
 chains on separate streams measured slower on MI355X -- ViT-tiny N=64 k=20:
 46.9 / 56.2 / 76.2 ms for 1 / 2 / 4 chains -- and was removed.)
 """
@@ -83,6 +85,15 @@ class _Denoiser:
         else:
             ops.ddim_step_(x, x0_raw, x0_out, coef)
 
+    def x0_(self, x, t, x0_out, ident, patches=None):
+        """Clamped x0-hat of f(x, t) into ``x0_out``; ``x`` is left exactly as it is (the
+        cold x0 sampler's forward: its update is :func:`ops.cold_step_`).  Fused: head
+        mode 1 with ``ident`` = the coefficient row {0, 1, 0, 1} (x_next = x_t)."""
+        if self.fused and FUSED_HEAD:
+            self.step_(x, t, 1, x0_out, ident, patches)
+            return
+        torch.clamp(self(x, t), -1.0, 1.0, out=x0_out)
+
     def __call__(self, x, t):
         if self.fused:
             out, _ = self.prog.forward(self.P, x, t, self.rng, False, save=False)
@@ -145,6 +156,16 @@ class _Rows:
     def step(self, t, mode: int, coef=None):
         x0 = None if mode == 2 else self.x0.view(self.shape)
         self.den.step_(self.x.view(self.shape), t, mode, x0, coef, patches=(self.pin, self.pin, self.w))
+
+    def predict_x0(self, t):
+        """One forward from the bf16 rows in ``pin`` with the clamp (mode 2) aimed at the
+        ``x0`` rows: ``x`` and ``pin`` stay as they are (the embedding reads only ``pin``)."""
+        self.den.step_(self.x0.view(self.shape), t, 2, patches=(self.pin, None, self.w))
+
+    def cold_step(self, t, algorithm: int):
+        """``x`` <- cold step from ``x0`` (per-sample ``t``), and its bf16 rows into ``pin``."""
+        N, C, H, W = self.shape
+        ops.cold_step_rows_(self.x, self.x0, t, N, C, H, W, self.p, algorithm, patches_out=self.pin)
 
     def image(self, xr):
         return ops.rows_to_image(xr, *self.shape, self.p)
@@ -294,31 +315,64 @@ class DDIMSampler:
         return [first] + [traj[i] for i in range(traj.shape[0])]
 
 
-class ColdSampler:
-    """Cold de-pixelation sampler: start from constant-colour images, x <- clamp(f(x, t)) for t = S..1."""
+COLD_RESTORE_GRAPHS = 8  # cached restoration loops (graph + buffers) per model
 
-    def __init__(self, model, device, use_graph: bool = True, steps: Optional[int] = None):
+
+class ColdSampler:
+    """Cold de-pixelation sampler, t = S..1, from constant-colour images (:meth:`sample`,
+    :meth:`sequence`) or from pixelated versions of given images (:meth:`restore`).
+
+    ``predict="prev"`` (a ``dataset: cold`` model, which predicts x_{t-1}): ``x <-
+    clamp(f(x, t))``, the reference's rule (`ViT_draft2drawing.py:259-288`).
+    ``predict="x0"`` (a ``dataset: cold_x0`` model, which predicts the clean image): with
+    x0-hat = clamp(f(x_t, t)) and D the training degradation, ``algorithm`` 1 is
+    ``x_{t-1} = D(x0-hat, t-1)`` and ``algorithm`` 2 ``x_{t-1} = x_t - D(x0-hat, t) +
+    D(x0-hat, t-1)`` (Bansal et al. 2022, Algorithms 1 and 2); each step is one forward
+    that leaves x0-hat in its own buffer plus one :func:`ops.cold_step_` launch, which also
+    writes the next step's bf16 patch rows.  The whole loop is one cached hipGraph."""
+
+    def __init__(self, model, device, use_graph: bool = True, steps: Optional[int] = None, predict: str = "prev",
+                 algorithm: int = 2):
+        if predict not in ("prev", "x0"):
+            raise ValueError(f"predict must be 'prev' or 'x0', got {predict!r}")
+        if algorithm not in (1, 2):
+            raise ValueError(f"algorithm must be 1 or 2, got {algorithm!r}")
         self.model = model
         self.device = torch.device(device)
         self.steps = steps or cold_steps(model.img_size[1])
         self.use_graph = use_graph and self.device.type == "cuda"
         self.H, self.W = model.img_size
         self.C = model.in_chans
+        self.predict = predict
+        self.algorithm = algorithm
 
     def _state(self, N: int):
         key = ("cold", N, self.steps, str(self.device))
+        if self.predict == "x0":
+            key += ("x0", self.algorithm)
         cache = _cache(self.model)
         st = cache.get(key)
         if st is not None and st["key"] == _Denoiser.key_of(self.model):
             return st
+        st = self._build(N, [[t] * N for t in range(self.steps, 0, -1)])
+        cache[key] = st
+        return st
+
+    def _build(self, N: int, levels):
+        """Buffers + loop for the step grid ``levels`` ([steps][N], descending): row i holds
+        the model's t of step i, or 0 for a sample that has not joined the grid yet (x0
+        prediction only: the step kernel skips it)."""
         den = _Denoiser(self.model, self.device)
         dev = self.device
         x = torch.zeros(N, self.C, self.H, self.W, device=dev)
-        ts = list(range(self.steps, 0, -1))
+        ts = [max(row) for row in levels]
         tt = torch.tensor(ts, dtype=torch.int64, device=dev).unsqueeze(1).expand(-1, N).contiguous()
         traj = torch.zeros(len(ts), N, self.C, self.H, self.W, device=dev)
         pbuf = _patch_rows(self.model, N, dev, den)
         rs = _rows_state(self.model, N, dev, den)
+        if self.predict == "x0":
+            loop = self._x0_loop(den, x, tt, torch.tensor(levels, dtype=torch.int64, device=dev), traj, pbuf, rs)
+            return {"key": den.key(), "x": x, "traj": traj, "loop": _GraphLoop(loop, dev)}
 
         def loop():
             if rs is not None:
@@ -333,9 +387,33 @@ class ColdSampler:
                 den.step_(x, tt[i], 2, patches=_chain_patches(pbuf, i == 0))
                 traj[i].copy_(x)
 
-        st = {"key": den.key(), "x": x, "traj": traj, "loop": _GraphLoop(loop, dev)}
-        cache[key] = st
-        return st
+        return {"key": den.key(), "x": x, "traj": traj, "loop": _GraphLoop(loop, dev)}
+
+    def _x0_loop(self, den, x, tt, tk, traj, pbuf, rs):
+        """The x0-prediction loop: per step one forward (x0-hat into its own buffer, x
+        untouched) and one cold-step launch with the per-sample levels ``tk[i]``; the
+        recorded states and the final ``x`` are clamped to [-1, 1]."""
+        alg = self.algorithm
+        x0 = torch.zeros_like(x) if rs is None else None
+        ident = torch.tensor([0.0, 1.0, 0.0, 1.0], device=x.device)
+        n = tt.shape[0]
+
+        def loop():
+            if rs is not None:
+                rs.begin(x)
+                for i in range(n):
+                    rs.predict_x0(tt[i])
+                    rs.cold_step(tk[i], alg)
+                    torch.clamp(rs.image(rs.x), -1.0, 1.0, out=traj[i])
+                torch.clamp(rs.image(rs.x), -1.0, 1.0, out=x)
+                return
+            for i in range(n):
+                den.x0_(x, tt[i], x0, ident, patches=_chain_patches(pbuf, i == 0))
+                ops.cold_step_(x, x0, tk[i], alg, patches_out=pbuf)
+                torch.clamp(x, -1.0, 1.0, out=traj[i])
+            x.clamp_(-1.0, 1.0)
+
+        return loop
 
     def _init(self, N, generator):
         c = torch.normal(0.0, 1.0, (N, self.C), generator=generator)
@@ -356,6 +434,58 @@ class ColdSampler:
         st["loop"].run(self.use_graph)
         traj = _unit_host(st["traj"])
         return [(init + 1) / 2] + [traj[i] for i in range(traj.shape[0])]
+
+    @torch.no_grad()
+    def restore(self, images: torch.Tensor, level, sequence: bool = False, unit: bool = True):
+        """Restore images from their pixelated versions: sample b starts from
+        ``pixelate(images[b], 2**level[b])`` and joins the shared step grid ``t =
+        max(level)..1`` at its own level (the cold counterpart of :func:`img2img`).
+
+        ``images`` [B,C,H,W] in [-1, 1]; ``level`` an int or one int per image, each in
+        ``0..cold_steps(W)``.  With ``predict="x0"`` a sample whose level is below step t is
+        skipped by the step kernel and stays exactly as it is (level 0: the clamped input
+        comes back); ``predict="prev"`` has no per-sample skip, so unequal levels raise
+        ``ValueError``.  The loop is one hipGraph cached per (B, levels, predict, algorithm),
+        at most ``COLD_RESTORE_GRAPHS`` per model, least recently used evicted.
+
+        Returns host images in [0, 1] (``unit=False``: in [-1, 1]); with ``sequence`` the
+        list [start, state after each step] instead, whose last entry is the result."""
+        from ..ops import reference as ref
+        if images.dim() == 3:
+            images = images.unsqueeze(0)
+        B = images.shape[0]
+        if tuple(images.shape[1:]) != (self.C, self.H, self.W):
+            raise ValueError(f"images must be [B, {self.C}, {self.H}, {self.W}], got {tuple(images.shape)}")
+        levels = [int(level)] * B if isinstance(level, int) else [int(v) for v in level]
+        top_ok = cold_steps(self.W)
+        if len(levels) != B or any(v < 0 or v > top_ok for v in levels):
+            raise ValueError(f"level: one int per image in 0..{top_ok}, got {level!r}")
+        if self.predict == "prev" and len(set(levels)) > 1:
+            raise ValueError("predict='prev' has no per-sample skip: all levels of one call must be equal")
+        images = images.detach().float().cpu()
+        start = torch.cat([ref.pixelate(images[b:b + 1], 2 ** v) for b, v in enumerate(levels)])
+        to_host = _unit_host if unit else (lambda v: v.cpu().clone())
+        top = max(levels)
+        if top == 0:  # nothing to step through
+            out = torch.clamp(start, -1.0, 1.0)
+            return [to_host(out)] if sequence else to_host(out)
+        key = ("cold_restore", B, tuple(levels), self.predict, self.algorithm, str(self.device))
+        cache = _cache(self.model)
+        st = cache.pop(key, None)
+        if st is not None:
+            cache[key] = st  # most recently used last
+        if st is None or st["key"] != _Denoiser.key_of(self.model):
+            cached = [c for c in cache if isinstance(c, tuple) and c[0] == "cold_restore" and c != key]
+            for old in cached[:max(0, len(cached) - COLD_RESTORE_GRAPHS + 1)]:
+                del cache[old]
+            st = self._build(B, [[t if v >= t else 0 for v in levels] for t in range(top, 0, -1)])
+            cache[key] = st
+        st["x"].copy_(start)
+        st["loop"].run(self.use_graph)
+        if not sequence:
+            return to_host(st["x"])
+        traj = to_host(st["traj"])
+        return [to_host(start)] + [traj[i] for i in range(traj.shape[0])]
 
 
 IMG2IMG_GRAPHS = 8  # cached img2img loops (graph + buffers) per model

@@ -346,13 +346,27 @@ class DiffusionVisionTransformer(nn.Module):
         return DDIMSampler(self, device, k=k, use_graph=False).sequence(N, generator=generator)
 
     @torch.no_grad()
-    def cold_sampler(self, device, k=10, N=49, generator=None, use_graph=True):
-        """Cold (de-pixelation) sampler (`ViT_draft2drawing.py:259-288`); ``k`` unused."""
+    def cold_sampler(self, device, k=10, N=49, generator=None, use_graph=True, predict="prev", algorithm=2):
+        """Cold (de-pixelation) sampler (`ViT_draft2drawing.py:259-288`); ``k`` unused.
+        ``predict="x0"`` for a model trained to predict the clean image (``dataset:
+        cold_x0``), with ``algorithm`` 1 or 2 of Bansal et al. 2022 (see ``ColdSampler``)."""
         from ..diffusion.samplers import ColdSampler
-        return ColdSampler(self, device, use_graph=use_graph).sample(N, generator=generator)
+        return ColdSampler(self, device, use_graph=use_graph, predict=predict,
+                           algorithm=algorithm).sample(N, generator=generator)
 
     @torch.no_grad()
-    def cold_diffusion_sequence(self, device, N=5, generator=None):
+    def cold_diffusion_sequence(self, device, N=5, generator=None, predict="prev", algorithm=2):
         """Cold trajectory recorder (`ViT_draft2drawing.py:290-309`)."""
         from ..diffusion.samplers import ColdSampler
-        return ColdSampler(self, device, use_graph=False).sequence(N, generator=generator)
+        return ColdSampler(self, device, use_graph=False, predict=predict,
+                           algorithm=algorithm).sequence(N, generator=generator)
+
+    @torch.no_grad()
+    def cold_restore(self, images, level, device=None, use_graph=True, predict="prev", algorithm=2,
+                     sequence=False):
+        """Restore ``images`` ([B,C,H,W] in [-1, 1]) from their pixelation at ``level`` (an int,
+        or one per image with ``predict="x0"``): ``ColdSampler.restore``; CPU images in [0, 1]."""
+        from ..diffusion.samplers import ColdSampler
+        device = device if device is not None else next(self.parameters()).device
+        return ColdSampler(self, device, use_graph=use_graph, predict=predict,
+                           algorithm=algorithm).restore(images, level, sequence=sequence)

@@ -8,6 +8,7 @@ PyTorch.
 """
 from __future__ import annotations
 
+import math
 from typing import Optional
 
 import torch
@@ -21,7 +22,7 @@ __all__ = [
     "linear_residual_fwd", "linear_gelu_fwd", "head_fwd", "smooth_l1_fwd_bwd", "img_to_tokgrad",
     "linear_dgrad", "linear_dgrad_gelu", "linear_wgrad", "layernorm_bwd", "attn_bwd", "embed_bwd",
     "sqnorm", "adamw_step", "advance_counters", "ddim_step", "ddim_step_", "randn_", "q_sample",
-    "pixelate_pair", "cold_batch", "gauss_batch", "head_step_rows_",
+    "pixelate_pair", "cold_batch", "gauss_batch", "head_step_rows_", "cold_step_", "cold_step_rows_",
     "image_to_rows", "rows_to_image", "embed_weight_rows", "patch_embed_cold_fwd", "ln_fold_",
 ]
 
@@ -593,6 +594,44 @@ def ddim_step_(x, x0_raw, x0_out, coef):
     xn, x0 = ref.ddim_step(x, x0_raw, _ddim_coef(coef, x))
     x.copy_(xn)
     x0_out.copy_(x0)
+
+
+def _cold_rows_out(patches_out, rows_bf16, t, batch: int):
+    """CPU: the patch rows of the samples a cold step updated (t >= 1); the others stay."""
+    if patches_out is None:
+        return
+    keep = (t.reshape(-1) >= 1).repeat_interleave(rows_bf16.shape[0] // batch)
+    patches_out[keep] = rows_bf16[keep]
+
+
+def cold_step_(x, x0, t, algorithm: int = 2, patches_out=None):
+    """Cold-diffusion sampling step of an x0-predicting model, in place on ``x``
+    (:func:`reference.cold_step`: algorithm 1 ``D(x0, t-1)``, algorithm 2 ``(x - D(x0, t))
+    + D(x0, t-1)``; per-sample ``t``, a sample with ``t <= 0`` is not touched).  ``x`` /
+    ``x0`` fp32 [B,C,H,W], distinct buffers, ``x0`` already clamped.  ``patches_out``
+    (bf16 [B*P, C*p*p], the patch size taken from its width): also the new ``x`` as
+    conv-order patch rows, the next step's :func:`patch_embed_fwd` ``patches_in``."""
+    C = x.shape[1]
+    patch = 0 if patches_out is None else math.isqrt(patches_out.shape[1] // C)
+    if patches_out is not None and patch * patch * C != patches_out.shape[1]:
+        raise ValueError("cold_step_: patches_out must be [B*P, C*p*p]")
+    if _hip(x):
+        return _ops().cold_step_(x, x0, t, int(algorithm), patch, patches_out)
+    x.copy_(ref.cold_step(x, x0, t, algorithm))
+    if patches_out is not None:
+        _cold_rows_out(patches_out, ref.patchify_bf16(x, patch), t, x.shape[0])
+
+
+def cold_step_rows_(x, x0, t, batch: int, C: int, H: int, W: int, patch: int, algorithm: int = 2, patches_out=None):
+    """:func:`cold_step_` on patch rows (``x`` / ``x0`` / ``patches_out`` [B*P, C*p*p] in the
+    head's output column order, :func:`image_to_rows`): the sampler's patch-row state is
+    updated where it lives and handed to the next step's patch embedding as bf16."""
+    if _hip(x):
+        return _ops().cold_step_rows_(x, x0, t, int(batch), int(C), int(H), int(W), int(patch), int(algorithm),
+                                      patches_out)
+    xi, x0i = (rows_to_image(v, batch, C, H, W, patch) for v in (x, x0))
+    x.copy_(image_to_rows(ref.cold_step(xi, x0i, t, algorithm), patch))
+    _cold_rows_out(patches_out, x.to(torch.bfloat16), t, batch)
 
 
 def randn_(out, rng, site: int):

@@ -441,6 +441,25 @@ def pixelate(img, factor: int):
     return F.interpolate(small, size=(H, W), mode="nearest")
 
 
+def cold_step(x, x0, t, algorithm: int = 2):
+    """Cold-diffusion sampling step of an x0-predicting model (Bansal et al. 2022):
+    with ``x0`` the clamped prediction and D = :func:`pixelate`, per sample with t >= 1
+
+    * algorithm 1 (naive):    ``D(x0, 2^(t-1))``
+    * algorithm 2 (improved): ``(x - D(x0, 2^t)) + D(x0, 2^(t-1))``, subtraction first;
+
+    a sample with ``t <= 0`` is returned unchanged.  ``x`` / ``x0`` fp32 [B,C,H,W], ``t`` int64 [B]."""
+    if algorithm not in (1, 2):
+        raise ValueError(f"cold_step: algorithm must be 1 or 2, got {algorithm!r}")
+    out = x.clone()
+    for b, tb in enumerate(int(v) for v in t.tolist()):
+        if tb <= 0:
+            continue
+        lo = pixelate(x0[b:b + 1], 2 ** (tb - 1))[0]
+        out[b] = (x[b] - pixelate(x0[b:b + 1], 2 ** tb)[0]) + lo if algorithm == 2 else lo
+    return out
+
+
 def img_to_tokgrad_op(dimg, N: int, patch: int):
     return img_to_tokgrad(dimg, N, patch)
 
