@@ -284,6 +284,11 @@ Tensor qkv_fwd(Tensor a, Tensor w, Tensor b, int64_t B, int64_t N, int64_t H, c1
 }
 
 int64_t gemm_tile_override_op(int64_t cfg) { return gemm_set_tile_override((int)cfg); }
+// (dma, BM, BN, waves, stages) of the launch an epilogue would take (host only: no launch)
+std::vector<int64_t> gemm_plan_op(int64_t epi, bool at, bool bt, int64_t M, int64_t N, int64_t K, int64_t splits) {
+  const GemmPlan pl = gemm_dma_plan((int)epi, at, bt, (int)M, (int)N, (int)K, (int)splits);
+  return {pl.dma ? 1 : 0, pl.bm, pl.bn, pl.waves, pl.stages};
+}
 // GEMM phase stamps (tools/ub_gemm_stamps.py): an int32 buffer, or None to stop
 void gemm_stamps_op(c10::optional<Tensor> buf) {
   if (buf.has_value() && buf->defined()) {
@@ -1273,6 +1278,7 @@ TORCH_LIBRARY(ddim_cold, m) {
   m.def("attn_fwd(Tensor qkv, float scale, Tensor rng, int site, float p, Tensor? keep_out=None) -> (Tensor, Tensor)");
   m.def("attn_keep_words(int B, int H, int N, int hd) -> int", &attn_keep_words_op);
   m.def("gemm_tile_override(int cfg) -> int", &gemm_tile_override_op);
+  m.def("gemm_plan(int epi, bool at, bool bt, int M, int N, int K, int splits=1) -> int[]", &gemm_plan_op);
   m.def("gemm_stamps(Tensor? buf) -> ()", &gemm_stamps_op);
   m.def("linear_residual_fwd(Tensor a, Tensor w, Tensor b, Tensor x, int N, Tensor rng, int site_drop, "
         "float p_drop, int site_dp, float p_dp, Tensor(a!)? st_out=None, Tensor(b!)? xb_out=None) -> Tensor");

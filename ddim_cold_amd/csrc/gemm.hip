@@ -421,22 +421,31 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_dma_kernel(GemmParams p) {
   gemm_dma_body<BM, BN, WM, WN, AT, BT, EPI, S>(p, tm, bid - tm * tiles_n, blockIdx.z);
 }
 
+// Ring depth of the LDS-DMA GEMM for BM x BN tiles (the one rule: launch_dma launches
+// by it, gemm_dma_plan reports it).  Keep every workgroup of the grid co-resident (one
+// round): a 4-stage ring allows 160 KiB / (4 x stage) workgroups per CU, a 3-stage ring
+// 4/3 of that; 256x128 fits 3 stages only, 256x192 only 2.
+static int dma_ring_stages(int bm, int bn, int workgroups, int ktiles_per_split) {
+  const int stage = bm * 128 + bn * 128;
+  if (3 * stage > 160 * 1024) return 2;
+  if (4 * stage > 160 * 1024) return 3;
+  const int per_cu4 = (160 * 1024) / (4 * stage);
+  return workgroups > 256 * per_cu4 && ktiles_per_split <= 8 ? 3 : 4;
+}
+
 template <int BM, int BN, int WM, int WN, bool AT, bool BT, int EPI>
 static void launch_dma(GemmParams p, int splits, hipStream_t stream) {
   const int total_kt = (p.K + BK - 1) / BK;
   p.ktiles_per_split = (total_kt + splits - 1) / splits;
   splits = (total_kt + p.ktiles_per_split - 1) / p.ktiles_per_split;
   const int tiles = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
-  // keep every workgroup of the grid co-resident (one round): a 4-stage ring
-  // allows 160 KiB / (4 x stage) workgroups per CU, a 3-stage ring 4/3 of that
   constexpr int stage = BM * 128 + BN * 128;
-  constexpr int per_cu4 = (160 * 1024) / (4 * stage);
   constexpr int threads = 64 * WM * WN;
   if constexpr (3 * stage > 160 * 1024) {  // 256x192: 2-stage ring (explicitly instantiated below)
     hipLaunchKernelGGL((gemm_dma_kernel<BM, BN, WM, WN, AT, BT, EPI, 2>), dim3(tiles, 1, splits), dim3(threads),
                        2 * stage, stream, p);
   } else {
-    if ((tiles * splits > 256 * per_cu4 && p.ktiles_per_split <= 8) || 4 * stage > 160 * 1024)
+    if (dma_ring_stages(BM, BN, tiles * splits, p.ktiles_per_split) == 3)
       hipLaunchKernelGGL((gemm_dma_kernel<BM, BN, WM, WN, AT, BT, EPI, 3>), dim3(tiles, 1, splits), dim3(threads),
                          3 * stage, stream, p);
     else
@@ -461,12 +470,18 @@ static void launch_cfg(GemmParams p, int splits, hipStream_t stream) {
 // (tag dispatch instead of `if constexpr`: hipcc 7.2 silently drops the host
 // stub of a kernel template first referenced inside an if-constexpr branch)
 // tile configs: 0 = 32x64, 1 = 64x64, 2 = 128x64, 3 = 128x128 (4 waves, 2x2);
-// 4 = 256x128, 5 = 128x128 (8 waves, 4x2: 512-thread workgroups, for M >= BIG_M)
+// 4 = 256x128, 5 = 128x128, 6 = 256x192 (8 waves, 4x2: 512-thread workgroups, for M >= BIG_M)
 constexpr int CFG_W8_256 = 4, CFG_W8_128 = 5, CFG_W8_192 = 6;
+// epilogues with no 4-wave workgroup reduction (HEAD / HEADL sum loss partials over 4 waves)
+constexpr bool wide8_epi(int epi) {
+  return epi == EPI_BF16 || epi == EPI_F32 || epi == EPI_QKV || epi == EPI_RESID || epi == EPI_GELU ||
+         epi == EPI_EMBED || epi == EPI_DGELU;
+}
+// ... and those the 256x192 tile is built for (plain operands only)
+constexpr bool big192_epi(bool bt, int epi) { return !bt && (epi == EPI_BF16 || epi == EPI_QKV || epi == EPI_GELU); }
 template <int EPI>
-struct Wide8 {  // epilogues with no 4-wave workgroup reduction (HEAD / HEADL sum loss partials over 4 waves)
-  static constexpr bool value = EPI == EPI_BF16 || EPI == EPI_F32 || EPI == EPI_QKV || EPI == EPI_RESID ||
-                                EPI == EPI_GELU || EPI == EPI_EMBED || EPI == EPI_DGELU;
+struct Wide8 {
+  static constexpr bool value = wide8_epi(EPI);
 };
 template <bool AT, bool BT, int EPI, bool OK = EPI != EPI_DGELU>
 struct Big256 {
@@ -476,7 +491,7 @@ template <bool AT, bool BT, int EPI>
 struct Big256<AT, BT, EPI, false> {
   static void go(GemmParams, int, hipStream_t) {}
 };
-template <bool AT, bool BT, int EPI, bool OK = !BT && (EPI == EPI_BF16 || EPI == EPI_QKV || EPI == EPI_GELU)>
+template <bool AT, bool BT, int EPI, bool OK = big192_epi(BT, EPI)>
 struct Big192 {  // 256x192 tiles, 2-stage ring (57 KiB per stage): N = 1152 in 6 column tiles
   static void go(GemmParams p, int splits, hipStream_t stream) { launch_dma<256, 192, 4, 2, AT, BT, EPI>(p, splits, stream); }
 };
@@ -561,27 +576,35 @@ static int pick_tiles(int M, int N, int K, int splits, bool at, bool bt, bool wi
   return ((M + 63) / 64) * ((N + 63) / 64) * splits >= 240 ? 1 : 0;
 }
 
+// The LDS-DMA path's tile config for an epilogue (launch_auto launches it,
+// gemm_dma_plan reports it).
+static int dma_cfg(int epi, bool at, bool bt, int M, int N, int K, int splits) {
+  // DGELU (input gradient through GELU + dropout, bf16 out) stays on 4-wave tiles at
+  // every measured M (M = 20,032: 25.5 vs 26.5 us; 40,064: 42.1 vs 49.9)
+  int cfg = pick_tiles(M, N, K, splits, at, bt, wide8_epi(epi) && epi != EPI_DGELU, epi == EPI_QKV);
+  // the GELU epilogue (erf-GELU + dropout per element, two bf16 outputs) is the
+  // heaviest in vector instructions: twice the waves of 32x64 tiles pay off on the
+  // sampler shape (M=4160: 6.56 vs 7.14 us, tools/gpu_tile_sweep3.sh); the other
+  // epilogues keep 64x64 there (QKV 11.45 vs 13.54, residual 6.65 vs 7.02)
+  // the patch embedding likewise (sampler M=4,096: 7.83 vs 9.08 us, tools/ub_sampler_ends.py)
+  if ((epi == EPI_GELU || epi == EPI_EMBED) && cfg == 1 && g_tile_override.load(std::memory_order_relaxed) < 0 &&
+      ((M + 31) / 32) * ((N + 63) / 64) <= 1024)
+    cfg = 0;
+  return cfg;
+}
+// the non-DMA GEMM (K % 64 != 0) takes 64x64 tiles from here, 32x64 below; no override
+static bool plain_big(int M, int N, int splits, bool at) {
+  return ((M + 63) / 64) * ((N + 63) / 64) * splits >= 240 || at;
+}
+
 template <bool AT, bool BT, int EPI>
 static void launch_auto(GemmParams p, int splits, hipStream_t stream) {
   const bool dma_ok = AT || p.K % 64 == 0;
   if (dma_ok) {
-    // DGELU (input gradient through GELU + dropout, bf16 out) stays on 4-wave tiles at
-    // every measured M (M = 20,032: 25.5 vs 26.5 us; 40,064: 42.1 vs 49.9)
-    int cfg = pick_tiles(p.M, p.N, p.K, splits, AT, BT, Wide8<EPI>::value && EPI != EPI_DGELU, EPI == EPI_QKV);
-    // the GELU epilogue (erf-GELU + dropout per element, two bf16 outputs) is the
-    // heaviest in vector instructions: twice the waves of 32x64 tiles pay off on the
-    // sampler shape (M=4160: 6.56 vs 7.14 us, tools/gpu_tile_sweep3.sh); the other
-    // epilogues keep 64x64 there (QKV 11.45 vs 13.54, residual 6.65 vs 7.02)
-    // the patch embedding likewise (sampler M=4,096: 7.83 vs 9.08 us, tools/ub_sampler_ends.py)
-    if ((EPI == EPI_GELU || EPI == EPI_EMBED) && cfg == 1 && g_tile_override.load(std::memory_order_relaxed) < 0 &&
-        ((p.M + 31) / 32) * ((p.N + 63) / 64) <= 1024)
-      cfg = 0;
-    DmaTiles<AT, BT, EPI>::launch(p, splits, stream, cfg);
+    DmaTiles<AT, BT, EPI>::launch(p, splits, stream, dma_cfg(EPI, AT, BT, p.M, p.N, p.K, splits));
     return;
   }
-  const int tiles64 = ((p.M + 63) / 64) * ((p.N + 63) / 64);
-  const bool big = tiles64 * splits >= 240 || AT;
-  if (big) launch_cfg<64, 64, 2, 2, AT, BT, EPI>(p, splits, stream);
+  if (plain_big(p.M, p.N, splits, AT)) launch_cfg<64, 64, 2, 2, AT, BT, EPI>(p, splits, stream);
   else launch_cfg<32, 64, 2, 2, AT, BT, EPI>(p, splits, stream);
 }
 
@@ -909,20 +932,46 @@ void gemm_nt(const GemmArgs& a, int epi, hipStream_t stream) {
   }
 }
 
-int gemm_nt_grid(int M, int N, int K) {
-  // mirrors launch_auto<false, false, EPI> (one split) for the epilogues that size a
-  // per-workgroup buffer from it (HEAD / HEADL: never 8-wave tiles)
-  const bool dma_ok = K % 64 == 0;
-  int bm = 64, bn = 64;
-  if (dma_ok) {
-    const int cfg = pick_tiles(M, N, K, 1, false, false, false);
-    const int bms[6] = {32, 64, 128, 128, 256, 128}, bns[6] = {64, 64, 64, 128, 128, 128};
-    bm = bms[cfg < 0 ? 0 : (cfg > 5 ? 5 : cfg)];
-    bn = bns[cfg < 0 ? 0 : (cfg > 5 ? 5 : cfg)];
-  } else if (((M + 63) / 64) * ((N + 63) / 64) < 240) {
-    bm = 32;
+// What launch_auto<at, bt, epi> would launch for an [M x N x K] problem in `splits` K
+// slices -- the tile after the fallbacks of DmaTiles / Launch8 / Big192 / Big256 and the
+// ring depth -- without launching anything.
+GemmPlan gemm_dma_plan(int epi, bool at, bool bt, int M, int N, int K, int splits) {
+  if (M < 1 || N < 1 || K < 1 || splits < 1) throw std::runtime_error("gemm_dma_plan: M, N, K, splits >= 1");
+  GemmPlan pl{};
+  const int total_kt = (K + BK - 1) / BK;
+  const int kps = (total_kt + splits - 1) / splits;
+  const int nsplit = (total_kt + kps - 1) / kps;
+  pl.dma = at || K % 64 == 0;
+  pl.waves = 4;
+  if (!pl.dma) {
+    pl.bm = plain_big(M, N, splits, at) ? 64 : 32;
+    pl.bn = 64;
+    pl.stages = 2;  // gemm_kernel double-buffers
+    return pl;
   }
-  return ((M + bm - 1) / bm) * ((N + bn - 1) / bn);
+  const int cfg = dma_cfg(epi, at, bt, M, N, K, splits);
+  if (at) { pl.bm = 64; pl.bn = 64; }                                // DmaTiles<true, BT>
+  else if (cfg == 0) { pl.bm = 32; pl.bn = 64; }
+  else if (cfg == 1) { pl.bm = 64; pl.bn = 64; }
+  else if (cfg == 2 || (cfg == 3 && bt)) { pl.bm = 128; pl.bn = 64; }  // DmaTiles<false, true>: BN = 64
+  else if (cfg == 3) { pl.bm = 128; pl.bn = 128; }
+  else {                                                             // Launch8
+    if (!wide8_epi(epi)) throw std::runtime_error("gemm: 8-wave tiles are not built for this epilogue");
+    pl.waves = 8;
+    pl.bm = 128; pl.bn = 128;
+    if (epi != EPI_DGELU) {
+      if (cfg == CFG_W8_192) { pl.bm = 256; pl.bn = big192_epi(bt, epi) ? 192 : 128; }
+      else if (cfg == CFG_W8_256) pl.bm = 256;
+    }
+  }
+  pl.stages = dma_ring_stages(pl.bm, pl.bn, ((M + pl.bm - 1) / pl.bm) * ((N + pl.bn - 1) / pl.bn) * nsplit, kps);
+  return pl;
+}
+
+int gemm_nt_grid(int M, int N, int K) {
+  // the epilogues that size a per-workgroup buffer from it (HEAD / HEADL: never 8-wave tiles)
+  const GemmPlan pl = gemm_dma_plan(EPI_HEAD, false, false, M, N, K, 1);
+  return ((M + pl.bm - 1) / pl.bm) * ((N + pl.bn - 1) / pl.bn);
 }
 
 int gemm_set_tile_override(int cfg) {

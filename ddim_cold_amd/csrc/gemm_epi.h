@@ -451,7 +451,9 @@ __device__ __forceinline__ void run_epilogue_scalar(const GemmParams& p, const f
           t = f2add(t, f2xor<4>(t));
           t = f2add(t, f2xor<8>(t));
           const int m = mb + i * 16 + 4 * g + r;
-          if (li == 0 && m < p.M)
+          // (a slot past N -- N % 32 == 0, but not a multiple of the wave's columns -- would
+          // be the next row's slot 0)
+          if (li == 0 && m < p.M && nb + sl * LN_SLOT < p.N)
             *reinterpret_cast<float2*>(p.st_out + 2 * ((size_t)fold_token_row<EPI>(p, m) * np_out + nb / LN_SLOT +
                                                        sl)) = t;
         }
@@ -855,7 +857,7 @@ struct VecEpi {
         for (int sl = 0; sl < SL; ++sl) {
           float2 t = cpart[sl];
           t = rowsum<1>(rowsum<0>(t));
-          if (sharer(g, li) == 0 && cls_i >= 0)
+          if (sharer(g, li) == 0 && cls_i >= 0 && colbase + sl * LN_SLOT < p.N)
             st2f(p.st_out + 2 * ((size_t)b * (p.tokens + 1) * np_out + colbase / LN_SLOT + sl), t);
         }
       }
@@ -877,7 +879,9 @@ struct VecEpi {
         for (int sl = 0; sl < SL; ++sl) {
           float2 t = part[i][sl];
           t = rowsum<1>(rowsum<0>(t));
-          if (sharer(g, li) == 0 && rowm[i] >= 0)
+          // a slot past N (N % 32 == 0, but not a multiple of the wave's columns) is not
+          // written: its address is the next row's slot 0 (past the buffer for the last row)
+          if (sharer(g, li) == 0 && rowm[i] >= 0 && colbase + sl * LN_SLOT < p.N)
             st2f(p.st_out + 2 * ((size_t)fold_token_row<EPI>(p, rowm[i]) * np_out + colbase / LN_SLOT + sl), t);
         }
     }

@@ -76,7 +76,18 @@ struct GemmArgs {
 void gemm_nt(const GemmArgs& a, int epi, hipStream_t stream);
 // workgroups gemm_nt launches for an [M x N x K] problem (one split)
 int gemm_nt_grid(int M, int N, int K);
-// force a GEMM tile config for every later launch (-1 = automatic choice; 0..5, see
+// host-only query: the kernel gemm_nt (at = bt = false), gemm_dgrad (bt) or gemm_wgrad
+// (at, bt) would launch for this epilogue and problem under the current tile override --
+// LDS-DMA ring or the plain K % 64 != 0 kernel, the tile after every fallback (e.g.
+// config 3 -> 128x64 for transposed B, DGELU 256 -> 128 rows), waves per workgroup and
+// ring depth.  Launches nothing.  Throws where the launch would (8-wave override on an
+// epilogue that is not built for it).
+struct GemmPlan {
+  bool dma = false;
+  int bm = 0, bn = 0, waves = 0, stages = 0;
+};
+GemmPlan gemm_dma_plan(int epi, bool at, bool bt, int M, int N, int K, int splits);
+// force a GEMM tile config for every later launch (-1 = automatic choice; 0..6, see
 // gemm.hip "tile configs"); returns the previous setting.  Tests / micro-benchmarks.
 int gemm_set_tile_override(int cfg);
 // phase stamps of every later LDS-DMA GEMM launch (GEMM_STAMP_WORDS words per

@@ -122,8 +122,11 @@ def qkv_fwd(a, w, b, B: int, N: int, H: int, fold=None):
 class gemm_tile:
     """Context manager forcing the GEMM tile config of every launch inside it
     (csrc/gemm.hip: 0 = 32x64, 1 = 64x64, 2 = 128x64, 3 = 128x128 with 4 waves;
-    4 = 256x128, 5 = 128x128 with 8 waves; -1 = automatic).  Tests and
-    micro-benchmarks; the automatic choice is the production path."""
+    4 = 256x128, 5 = 128x128, 6 = 256x192 with 8 waves; -1 = automatic).  Config 6 is
+    built for the plain-operand BF16 / QKV / GELU epilogues only: elsewhere it runs as
+    256x128 (128x128 for the GELU input gradient); ``torch.ops.ddim_cold.gemm_plan``
+    tells which tile and ring depth a launch takes.  Tests and micro-benchmarks; the
+    automatic choice is the production path."""
 
     def __init__(self, cfg: int):
         self.cfg = int(cfg)
@@ -188,8 +191,8 @@ def head_step_(a, w, b, x, x0_out, coef, patch: int, mode: int, fold=None, patch
     DDIM update (``x0_out`` gets the clamped x0-hat; ``coef`` a device row of
     ``ddim_coefficients``), mode 2 = clamp only (cold sampler), mode 4 = mode 1 with
     one coefficient row per sample (``coef`` [B, 4]; img2img: the row {0, 1, 0, 1}
-    leaves a sample that has not reached its start step unchanged).  ``patches_out``
-    (GPU): also the new ``x`` as bf16 patch rows, for the next step's
+    leaves a sample that has not reached its start step unchanged).  ``patches_out``:
+    also the new ``x`` as bf16 patch rows, for the next step's
     :func:`patch_embed_fwd` (``patches_in``)."""
     st, c, eps, _, _ = _fold_args(fold)
     if _hip(a):
@@ -198,10 +201,12 @@ def head_step_(a, w, b, x, x0_out, coef, patch: int, mode: int, fold=None, patch
     x0_raw = ref.head_fwd(a, w, b, B, C, H, W, patch, st, c, eps)
     if mode == 2:
         x.copy_(torch.clamp(x0_raw, -1.0, 1.0))
-        return
-    xn, x0 = ref.ddim_step(x, x0_raw, _ddim_coef(coef, x))
-    x.copy_(xn)
-    x0_out.copy_(x0)
+    else:
+        xn, x0 = ref.ddim_step(x, x0_raw, _ddim_coef(coef, x))
+        x.copy_(xn)
+        x0_out.copy_(x0)
+    if patches_out is not None:
+        patches_out.copy_(ref.patchify_bf16(x, patch).view(patches_out.shape))
 
 
 def image_to_rows(x, patch: int):

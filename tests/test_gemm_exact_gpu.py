@@ -1,0 +1,309 @@
+"""The GEMMs of csrc/gemm.hip against exact integer probes (ops/gemm_check.py), bit for
+bit, over every tile configuration, ring depth, operand reader and edge.
+
+With small-integer bf16 operands every partial sum is an exact fp32 integer in any
+summation order, so the tolerance is zero; a position probe (one-hot rows against a
+coded operand) names the element each output was read from.  Every case asserts through
+``torch.ops.ddim_cold.gemm_plan`` that the (path, tile, ring depth) it names is the one
+that ran.  Caller-provided outputs sit in canaried buffers (writes past row M / column N).
+
+Tile configs (``ops.gemm_tile``): 0 = 32x64, 1 = 64x64, 2 = 128x64, 3 = 128x128 (4 waves);
+4 = 256x128, 5 = 128x128, 6 = 256x192 (8 waves).  Config 6 is built for the plain-operand
+BF16 / QKV / GELU epilogues and runs as 256x128 elsewhere (128x128 for DGELU); config 3 is
+128x64 for transposed B; DGELU's 256-row config is the 128-row one.  Ring depth: 256x192
+always 2, 256x128 always 3, the others 3 when the grid exceeds 256 x per_cu4 workgroups
+with at most 8 k-tiles per slice, else 4.  ``linear_wgrad_multi`` has its own kernel and
+no plan: its 64 / 128 tile follows the token count (>= 16,384: 128x128).
+
+A new tile configuration joins TILES in ops/gemm_check.py and with it the grids of
+sections (a) and (b) here.
+
+Out of scope (non-integer epilogue arithmetic, kept on the tolerance tests): the
+LayerNorm-fold consumers, HEADL, HEAD modes 1 / 4, GELU's ``h``."""
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+from ddim_cold_amd import ops
+from ddim_cold_amd.ops import gemm_check as gc
+
+DEV = "cuda"
+ALL_TILES = sorted(gc.TILES)
+TILES_4W = [0, 1, 2, 3]
+
+
+@pytest.fixture(autouse=True)
+def _native():
+    from ddim_cold_amd.ops import _ext
+    _ext.load(raise_on_error=True)
+
+
+def plan(epi, M, N, K, at=False, bt=False, splits=1):
+    """(dma, BM, BN, waves, stages) of the launch under the current tile override."""
+    return tuple(int(v) for v in torch.ops.ddim_cold.gemm_plan(epi, at, bt, M, N, K, splits))
+
+
+def expected_tile(cfg, epi, bt=False):
+    """(BM, BN, waves) of config ``cfg`` after the documented fallbacks."""
+    if cfg == 6 and not (not bt and epi in (gc.EPI_BF16, gc.EPI_QKV, gc.EPI_GELU)):
+        cfg = 4
+    if cfg == 4 and epi == gc.EPI_DGELU:
+        cfg = 5
+    if cfg == 3 and bt:
+        cfg = 2
+    return gc.TILES[cfg]
+
+
+def expected_stages(bm, bn, M, N, K, splits=1):
+    stage = (bm + bn) * 128
+    if 3 * stage > 160 * 1024:
+        return 2
+    if 4 * stage > 160 * 1024:
+        return 3
+    kt = -(-K // 64)
+    kps = -(-kt // splits)
+    wgs = -(-M // bm) * -(-N // bn) * -(-kt // kps)
+    return 3 if wgs > 256 * ((160 * 1024) // (4 * stage)) and kps <= 8 else 4
+
+
+def assert_plan(cfg, epi, M, N, K, bt=False, splits=1, stages=None):
+    """The launch is the LDS-DMA kernel on config ``cfg``'s (documented) tile; returns (BM, BN)."""
+    bm, bn, waves = expected_tile(cfg, epi, bt)
+    st = expected_stages(bm, bn, M, N, K, splits)
+    assert stages is None or st == stages, f"the case was built for ring depth {stages}, the rule gives {st}"
+    got = plan(epi, M, N, K, False, bt, splits)
+    assert got == (1, bm, bn, waves, st), f"plan {got} != {(1, bm, bn, waves, st)} (cfg {cfg} epi {epi} {M}x{N}x{K})"
+    return bm, bn
+
+
+# ----------------------------------------------------------------------------- (a) tile x edge grid
+@pytest.mark.parametrize("K", gc.EDGE_KS)
+@pytest.mark.parametrize("cfg", ALL_TILES)
+def test_linear_tile_edges(cfg, K):
+    bm, bn, _ = gc.TILES[cfg]
+    with ops.gemm_tile(cfg):
+        for M in gc.edge_ms(bm):
+            for N in gc.edge_ns(bn):
+                tiles = {f32: assert_plan(cfg, gc.EPI_F32 if f32 else gc.EPI_BF16, M, N, K) for f32 in (False, True)}
+                assert tiles[False] == (bm, bn)  # bf16 output: every config is real, 256x192 included
+                gc.run_linear(M, N, K, DEV, tile=tiles.get)
+
+
+# ----------------------------------------------------------------------------- (b) ring depth
+PAIRED = ((False, True), (True, False))  # bf16 + bias, fp32 without: output type paired with bias
+
+
+@pytest.mark.parametrize("K,stages", [(512, 3), (576, 4), (64, 3), (128, 3)])
+@pytest.mark.parametrize("cfg", gc.TWO_DEPTH_TILES)
+def test_ring_depth_over_threshold(cfg, K, stages):
+    """Just over 256 x per_cu4 workgroups: 8 k-tiles take the 3-stage ring, 9 the 4-stage
+    one; 1 and 2 k-tiles are fewer than the 3-stage prologue issues."""
+    M, N = gc.depth_shape(cfg)
+    with ops.gemm_tile(cfg):
+        tiles = {f32: assert_plan(cfg, gc.EPI_F32 if f32 else gc.EPI_BF16, M, N, K, stages=stages) for f32 in (False, True)}
+        gc.run_linear(M, N, K, DEV, tile=tiles.get, combos=PAIRED)
+
+
+@pytest.mark.parametrize("K", gc.SHORT_KS)
+@pytest.mark.parametrize("cfg", gc.TWO_DEPTH_TILES)
+def test_ring_depth4_short_k(cfg, K):
+    """Fewer k-tiles than the 4-stage prologue issues."""
+    bm, bn, _ = gc.TILES[cfg]
+    M, N = bm + 1, bn + 4
+    with ops.gemm_tile(cfg):
+        tiles = {f32: assert_plan(cfg, gc.EPI_F32 if f32 else gc.EPI_BF16, M, N, K, stages=4) for f32 in (False, True)}
+        gc.run_linear(M, N, K, DEV, tile=tiles.get, combos=PAIRED)
+
+
+@pytest.mark.parametrize("K", gc.FIXED_DEPTH_KS)
+@pytest.mark.parametrize("cfg,stages", gc.FIXED_DEPTH_TILES)
+def test_ring_depth_fixed(cfg, stages, K):
+    """256x128 is always 3 stages deep, 256x192 always 2 (ragged M and N)."""
+    bm, bn, _ = gc.TILES[cfg]
+    M, N = 2 * bm + 17, bn + 4
+    with ops.gemm_tile(cfg):
+        assert assert_plan(cfg, gc.EPI_BF16, M, N, K, stages=stages) == (bm, bn)
+        gc.run_linear(M, N, K, DEV, tile=(bm, bn), combos=((False, True), (False, False)))
+
+
+# ----------------------------------------------------------------------------- (c) non-DMA path
+@pytest.mark.parametrize("K", gc.PLAIN_KS)
+@pytest.mark.parametrize("M,N,bm", [(*gc.PLAIN_SHAPES[0], 32), (*gc.PLAIN_SHAPES[1], 64)])
+def test_plain_kernel(M, N, bm, K):
+    """K % 64 != 0: ``gemm_kernel`` on 32x64 tiles under 240 64x64 tiles, 64x64 from there;
+    the tile override is ignored."""
+    want = (0, bm, 64, 4, 2)
+    for epi in (gc.EPI_BF16, gc.EPI_F32):
+        assert plan(epi, M, N, K) == want
+    gc.run_linear(M, N, K, DEV, tile=(bm, 64), combos=PAIRED)
+    with ops.gemm_tile(3):
+        assert plan(gc.EPI_BF16, M, N, K) == want and plan(gc.EPI_F32, M, N, K) == want
+        gc.run_linear(M, N, K, DEV, tile=(bm, 64), combos=PAIRED, seed=12)
+
+
+# ----------------------------------------------------------------------------- (d) epilogue index maps
+@pytest.mark.parametrize("cfg", ALL_TILES)
+@pytest.mark.parametrize("B,N,H,D", gc.QKV_SHAPES + (gc.QKV_SHAPE_HD16,))
+def test_qkv_exact(cfg, B, N, H, D):
+    with ops.gemm_tile(cfg):
+        tile = assert_plan(cfg, gc.EPI_QKV, B * N, 3 * D, D)
+        assert tile == gc.TILES[cfg][:2]  # QKV: 256x192 is real
+        gc.run_qkv(B, N, H, D, DEV, tile=tile)
+
+
+@pytest.mark.parametrize("cfg", ALL_TILES)
+@pytest.mark.parametrize("M,tokens,Dout,K", gc.RESID_SHAPES)
+def test_residual_exact(cfg, M, tokens, Dout, K):
+    with ops.gemm_tile(cfg):
+        tile = assert_plan(cfg, gc.EPI_RESID, M, Dout, K)
+        assert cfg != 6 or tile == (256, 128)  # not built for RESID: the documented fallback
+        gc.run_residual(M, tokens, Dout, K, DEV, tile=tile)
+
+
+@pytest.mark.parametrize("cfg", ALL_TILES)
+@pytest.mark.parametrize("M,N,K", gc.GELU_SHAPES)
+def test_gelu_exact(cfg, M, N, K):
+    with ops.gemm_tile(cfg):
+        tile = assert_plan(cfg, gc.EPI_GELU, M, N, K)
+        assert tile == gc.TILES[cfg][:2]
+        gc.run_gelu(M, N, K, DEV, tile=tile)
+
+
+@pytest.mark.parametrize("cfg", TILES_4W)
+@pytest.mark.parametrize("B,C,H,W,p,D", gc.HEAD_GEOMS)
+def test_head_exact(cfg, B, C, H, W, p, D):
+    N = (H // p) * (W // p) + 1
+    with ops.gemm_tile(cfg):
+        tile = assert_plan(cfg, gc.EPI_HEAD, B * N, C * p * p, D)
+        gc.run_head(B, C, H, W, p, D, DEV, tile=tile)
+
+
+@pytest.mark.parametrize("cfg", [4, 5, 6])
+def test_head_rejects_8_wave_tiles(cfg):
+    """The head epilogues reduce over 4 waves: an 8-wave override fails loudly, in the plan
+    and in the launch."""
+    B, C, H, W, p, D = gc.HEAD_GEOMS[0]
+    N = (H // p) * (W // p) + 1
+    g = torch.Generator().manual_seed(0)
+    a, w = gc.int_operands((B * N, D), -1, 1, g, device=DEV), gc.int_operands((C * p * p, D), -1, 1, g, device=DEV)
+    b = torch.zeros(C * p * p, device=DEV)
+    with ops.gemm_tile(cfg):
+        with pytest.raises(RuntimeError):
+            plan(gc.EPI_HEAD, B * N, C * p * p, D)
+        with pytest.raises(RuntimeError):
+            ops.head_fwd(a, w, b, B, C, H, W, p)
+            torch.cuda.synchronize()
+
+
+@pytest.mark.parametrize("cfg", ALL_TILES)
+@pytest.mark.parametrize("B,C,H,W,p,D", gc.EMBED_GEOMS)
+def test_patch_embed_exact(cfg, B, C, H, W, p, D):
+    M, K = B * (H // p) * (W // p), C * p * p
+    with ops.gemm_tile(cfg):
+        if K % 64 == 0:
+            tile = assert_plan(cfg, gc.EPI_EMBED, M, D, K)
+        else:  # p = 4: K = 48, the non-DMA kernel whatever the override
+            assert plan(gc.EPI_EMBED, M, D, K) == (0, 32, 64, 4, 2)
+            tile = (32, 64)
+        gc.run_patch_embed(B, C, H, W, p, D, DEV, tile=tile)
+
+
+@pytest.mark.parametrize("cfg", ALL_TILES)
+@pytest.mark.parametrize("B,C,H,W,p,D", gc.EMBED_STAT_GEOMS)
+def test_patch_embed_row_statistics_exact(cfg, B, C, H, W, p, D):
+    """The LayerNorm-fold producer of the embedding (``ln_st`` / ``xb_out`` in canaries) at
+    widths that are a multiple of 32 but not of the tile: a slot past N must not be written."""
+    with ops.gemm_tile(cfg):
+        tile = assert_plan(cfg, gc.EPI_EMBED, B * (H // p) * (W // p), D, C * p * p)
+        gc.run_patch_embed(B, C, H, W, p, D, DEV, tile=tile, stats=True)
+
+
+# ----------------------------------------------------------------------------- (e) dropout placement
+@pytest.mark.parametrize("p", gc.DROPOUT_PS)
+@pytest.mark.parametrize("cfg", ALL_TILES)
+def test_dropout_placement(cfg, p):
+    """``out == 0`` is the reference's drop set and the survivors its value bit for bit
+    (the kernels scale by the fp32 ``1 / (1 - p)`` product the reference's division equals
+    at these p and values; GELU's ``h`` keeps the tolerance: erf is not exact), at ragged
+    M and N under every tile."""
+    bm, bn, _ = gc.TILES[cfg]
+    M, N = 2 * bm + 17, bn + 4
+    tokens = gc.small_prime_factor(M)
+    with ops.gemm_tile(cfg):
+        tile = assert_plan(cfg, gc.EPI_RESID, M, N, 64)
+        gc.run_dropout("resid_drop", M, N, p, DEV, tile, tokens=tokens)
+        gc.run_dropout("resid_dp", M, N, p, DEV, tile, tokens=tokens)
+        gc.run_dropout("gelu", M, N, p, DEV, assert_plan(cfg, gc.EPI_GELU, M, N, 64))
+        B, H, W, pp = gc.embed_dropout_geom(M)
+        gc.run_dropout_embed(B, H, W, pp, N, p, DEV, assert_plan(cfg, gc.EPI_EMBED, B * 81, N, 3 * pp * pp))
+        Nd = gc.dgrad_width(cfg) if cfg < 6 else bn + 8
+        gc.run_dropout("dgelu", M, Nd, p, DEV, assert_plan(cfg, gc.EPI_DGELU, M, Nd, 64, bt=True))
+
+
+# ----------------------------------------------------------------------------- (f) dgrad
+@pytest.mark.parametrize("Nout", gc.DGRAD_NOUT)
+@pytest.mark.parametrize("cfg", ALL_TILES[:6])
+def test_dgrad_exact(cfg, Nout):
+    K = gc.dgrad_width(cfg)
+    splits = [1] + gc.dgrad_splits(Nout)
+    with ops.gemm_tile(cfg):
+        for M in gc.DGRAD_MS:
+            for s in splits:
+                for epi in (gc.EPI_F32, gc.EPI_BF16):
+                    if Nout % 64 == 0:
+                        tile = assert_plan(cfg, epi, M, K, Nout, bt=True, splits=s)
+                    else:  # the non-DMA kernel, transposed-B reader
+                        tile = (64 if -(-M // 64) * -(-K // 64) * s >= 240 else 32, 64)
+                        assert plan(epi, M, K, Nout, bt=True, splits=s) == (0, *tile, 4, 2)
+            gc.run_dgrad(M, Nout, K, DEV, tile=tile, splits=splits)
+
+
+@pytest.mark.parametrize("M,Nout,K,s", gc.DGRAD_LN_CASES)
+def test_dgrad_slices_into_layernorm_bwd(M, Nout, K, s):
+    assert s == gc.dgrad_splits(Nout)[-1]  # the largest split the binding accepts
+    gc.run_dgrad_ln(M, Nout, K, s, DEV)
+
+
+@pytest.mark.parametrize("with_wt", [False, True])
+@pytest.mark.parametrize("cfg", ALL_TILES[:6])
+@pytest.mark.parametrize("M,Nout", gc.DGELU_SHAPES)
+def test_dgrad_gelu_exact(cfg, M, Nout, with_wt):
+    K = gc.dgrad_width(cfg)
+    with ops.gemm_tile(cfg):
+        tile = assert_plan(cfg, gc.EPI_DGELU, M, K, Nout, bt=not with_wt)
+        assert cfg < 4 or tile == (128, 128)  # DGELU's 8-wave tile is always 128x128
+        gc.run_dgrad_gelu(M, Nout, K, DEV, tile=tile, with_wt=with_wt)
+
+
+# ----------------------------------------------------------------------------- (g) wgrad
+def _wgrad_splits(T, Nout, K):  # csrc/bindings.cpp linear_wgrad
+    tiles = -(-Nout // 64) * -(-K // 64)
+    return max(1, min(8, -(-256 // tiles), -(-T // 64)))
+
+
+@pytest.mark.parametrize("T", gc.WGRAD_TOKENS)
+def test_wgrad_exact(T):
+    for Nout, K, with_db in gc.wgrad_shapes():
+        for db in (with_db, not with_db):
+            assert plan(gc.EPI_ATOMIC, Nout, K, T, at=True, bt=True, splits=_wgrad_splits(T, Nout, K))[:4] == (1, 64, 64, 4)
+            gc.run_wgrad(T, Nout, K, DEV, db)
+
+
+@pytest.mark.parametrize("store", [False, True])
+@pytest.mark.parametrize("T", gc.WGRAD_TOKENS)
+def test_wgrad_multi_exact(T, store):
+    gc.run_wgrad_multi(T, gc.wgrad_shapes(), DEV, store)
+
+
+@pytest.mark.parametrize("store", [False, True])
+def test_wgrad_multi_wide_split_tail(store):
+    """>= 16,384 tokens: 128x128 tiles; 10 tiles, all in the K-split tail (6 pieces each):
+    exact and bit-identical over three launches."""
+    gc.run_wgrad_multi(gc.WGRAD_BIG_TOKENS, gc.WGRAD_BIG_SHAPES, DEV, store, lo=-2, hi=2, repeats=3)
+
+
+@pytest.mark.parametrize("T,store", [(200, False), (200, True), (gc.WGRAD_BIG_TOKENS, False), (gc.WGRAD_BIG_TOKENS, True)])
+def test_wgrad_multi_sq_partials(T, store):
+    shapes = gc.wgrad_shapes() if T < 16384 else gc.WGRAD_BIG_SHAPES
+    gc.run_wgrad_sq(T, shapes, DEV, store)

@@ -4,10 +4,14 @@
   0 = 32x64, 1 = 64x64, 2 = 128x64, 3 = 128x128   (4 waves)
   4 = 256x128, 5 = 128x128                          (8 waves, 512-thread workgroups;
                                                      the automatic choice for M >= 16,384)
+  6 = 256x192                                       (8 waves, 2-stage ring; built for the
+                                                     plain-operand BF16 / QKV / GELU epilogues,
+                                                     the automatic choice for QKV with N % 192 == 0)
 
 Shapes include the vit_small_200 training rows (M = 32 * 626 = 20,032, not a
 multiple of 256), ragged M / N, the K = 1,152 QKV input gradient, and the
-LayerNorm-fold consumer and producer epilogues."""
+LayerNorm-fold consumer and producer epilogues.  Bit-exact integer probes of the same
+grid at small shapes: tests/test_gemm_exact_gpu.py."""
 import pytest
 import torch
 
@@ -18,6 +22,7 @@ from ddim_cold_amd.ops import reference as ref
 
 DEV = "cuda"
 TILES = [0, 1, 2, 3, 4, 5]
+TILES_192 = TILES + [6]  # the epilogues the 256x192 tile is built for
 
 
 @pytest.fixture(autouse=True)
@@ -42,7 +47,7 @@ def bf(*shape, scale=1.0):
     return (torch.randn(*shape, device=DEV) * scale).to(torch.bfloat16)
 
 
-@pytest.mark.parametrize("tile", TILES)
+@pytest.mark.parametrize("tile", TILES_192)
 @pytest.mark.parametrize("B,N,H,D", [(32, 626, 6, 384), (3, 17, 2, 128)])
 def test_qkv_tiles(tile, B, N, H, D):
     a, w, b = bf(B * N, D), bf(3 * D, D, scale=0.05), torch.randn(3 * D, device=DEV)
@@ -67,7 +72,7 @@ def test_residual_producer_tiles(tile, M, N, pd, pdp):
     close(st, ref.row_stats(y), 1e-3, 1e-4, "row statistics slots")
 
 
-@pytest.mark.parametrize("tile", TILES)
+@pytest.mark.parametrize("tile", TILES_192)
 def test_gelu_fold_tiles(tile):
     M, K, Hm = 20032, 384, 384
     x = torch.randn(M, K, device=DEV) * 2 + 0.5
