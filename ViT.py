@@ -35,13 +35,22 @@ from ddim_cold_amd.utils.images import get_next_path, save_grid, save_sequence_g
 @click.option("--seq_n", default=6)
 @click.option("--seq_k", default=100)
 @click.option("--seed", default=0)
-def main(sample_n, acc_k, ckpt, model_name, out_dir, seq_n, seq_k, seed):
+@click.option("--ema", is_flag=True, help="sample from the EMA weights: 'ema_state_dict' of a lastepoch.pkl-style "
+              "--ckpt, else the <ckpt>_ema sibling file (bestloss.pkl -> bestloss_ema.pkl)")
+def main(sample_n, acc_k, ckpt, model_name, out_dir, seq_n, seq_k, seed, ema):
     """DDIM sampling from a DiffusionVisionTransformer checkpoint."""
     from ddim_cold_amd.models import build_model
-    from ddim_cold_amd.train.checkpoint import load_weights
+    from ddim_cold_amd.train.checkpoint import load_weights, resolve_ema_checkpoint
     device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
     model = build_model(model_name, init_order="vit")  # ViT.py:184 draw order (weights are loaded anyway)
-    if os.path.isfile(ckpt):
+    if ema:
+        try:
+            path, key = resolve_ema_checkpoint(ckpt)
+        except FileNotFoundError as e:
+            sys.exit(f"error: {e}")
+        load_weights(model, path, strict=True, ema=key)
+        print(f"loaded EMA weights from {path}" + (" ['ema_state_dict']" if key else ""))
+    elif os.path.isfile(ckpt):
         load_weights(model, ckpt, strict=True)
     else:
         print(f"warning: {ckpt} not found, sampling from random-init weights", file=sys.stderr)

@@ -31,6 +31,9 @@ from ddim_cold_amd.models.vit import (Attention, Block, DiffusionVisionTransform
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--ckpt", default=os.path.join(HERE, "Saved_Models", "20220822vit_tiny_diffusion", "bestloss.pkl"))
+    ap.add_argument("--ema", action="store_true",
+                    help="use the EMA weights: 'ema_state_dict' of a lastepoch.pkl-style --ckpt, else the "
+                         "<ckpt>_ema sibling file (bestloss.pkl -> bestloss_ema.pkl)")
     ap.add_argument("--draft", default=os.path.join(HERE, "Saved_Models", "draft.jpg"))
     ap.add_argument("--out_dir", default=os.path.join(HERE, "Saved_Models"))
     ap.add_argument("--k", type=int, default=10)
@@ -46,11 +49,18 @@ def main(argv=None):
     from ddim_cold_amd.data.synthetic import synthetic_pool
     from ddim_cold_amd.diffusion.samplers import img2img
     from ddim_cold_amd.models import build_model
-    from ddim_cold_amd.train.checkpoint import load_weights
+    from ddim_cold_amd.train.checkpoint import load_weights, resolve_ema_checkpoint
     from ddim_cold_amd.utils.images import get_next_path, save_grid, save_sequence_grid
     device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
     model = build_model("vit_tiny")
-    if os.path.isfile(a.ckpt):
+    if a.ema:
+        try:
+            path, key = resolve_ema_checkpoint(a.ckpt)
+        except FileNotFoundError as e:
+            sys.exit(f"error: {e}")
+        load_weights(model, path, strict=True, ema=key)
+        print(f"loaded EMA weights from {path}" + (" ['ema_state_dict']" if key else ""))
+    elif os.path.isfile(a.ckpt):
         load_weights(model, a.ckpt, strict=True)
     else:
         print(f"warning: {a.ckpt} not found, using random-init weights", file=sys.stderr)

@@ -40,7 +40,11 @@ for smoke runs), ``comm_layout`` (fixed data-parallel gradient-exchange layout
 instead of ``comm_autotune``), ``force_segments`` (testing: run the data-parallel
 step on a 1-rank process group), ``graph_steps`` (optimizer steps per hipGraph
 replay, default 4; the batch rows come from a device table indexed by the step
-counter, so one replay runs K whole steps).
+counter, so one replay runs K whole steps), ``weight_ema`` (decay of an exponential
+moving average of the weights kept by the optimizer launch, 0 = off; checkpointed as
+``'ema_state_dict'`` / ``bestloss_ema.pkl``), ``weight_ema_warmup`` (ramp the decay as
+min(weight_ema, (1 + t) / (10 + t)), default true), ``ema_eval`` (validate, and pick
+``bestloss``, on the EMA weights; needs ``weight_ema``).
 """
 from __future__ import annotations
 
@@ -93,6 +97,9 @@ class ExperimentConfig:
     comm_layout: Optional[str] = None  # data parallel: '[graph-]overlap-<blocks>' | '[graph-]inline-1' (skips comm_autotune)
     force_segments: bool = False  # testing: the data-parallel step (1-rank RCCL group, comm stream) at num_gpus 1
     graph_steps: int = 4          # optimizer steps per replayed hipGraph (1: one graph per step)
+    weight_ema: float = 0.0       # decay of the weight EMA (0: none kept); typical 0.999 - 0.9999
+    weight_ema_warmup: bool = True  # decay ramps as min(weight_ema, (1 + t) / (10 + t))
+    ema_eval: bool = False        # epoch validation (logged metric, bestloss decision) on the EMA weights
 
     # ------------------------------------------------------------------ derived
     @property
@@ -131,6 +138,10 @@ class ExperimentConfig:
                 raise ValueError(f"unknown comm_layout {self.comm_layout!r}")
         if self.graph_steps < 1:
             raise ValueError("graph_steps must be >= 1")
+        if not 0.0 <= float(self.weight_ema) < 1.0:
+            raise ValueError(f"weight_ema must be in [0, 1), got {self.weight_ema}")
+        if self.ema_eval and not self.weight_ema > 0:
+            raise ValueError("ema_eval needs weight_ema > 0")
         if not self.synthetic and not all(self.dataStorage):
             raise ValueError("dataStorage needs [train_dir, val_dir] unless synthetic: true")
         return self

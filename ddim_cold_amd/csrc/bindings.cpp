@@ -1034,7 +1034,7 @@ void sqnorm(Tensor g, Tensor out, double scale, int64_t lz_lo, int64_t lz_hi) {
 
 void adamw_step(Tensor p, Tensor g, Tensor m, Tensor v, c10::optional<Tensor> pbf, Tensor sq, Tensor step,
                 Tensor hyper, double grad_scale, int64_t zero_hi, int64_t lz_lo, int64_t lz_hi,
-                c10::optional<Tensor> lazy_decay) {
+                c10::optional<Tensor> lazy_decay, c10::optional<Tensor> ema, double ema_decay, bool ema_warmup) {
   CHECK_IN(p, F32); CHECK_IN(g, F32); CHECK_IN(m, F32); CHECK_IN(v, F32); CHECK_IN(sq, F32); CHECK_IN(step, I64);
   CHECK_IN(hyper, F32);
   const c10::DeviceGuard guard(p.device());
@@ -1053,9 +1053,17 @@ void adamw_step(Tensor p, Tensor g, Tensor m, Tensor v, c10::optional<Tensor> pb
     CHECK_IN((*lazy_decay), F32);
     ld = lazy_decay->data_ptr<float>();
   }
+  float* ep = nullptr;
+  if (ema.has_value() && ema->defined()) {
+    CHECK_IN((*ema), F32);
+    TORCH_CHECK(ema->numel() == n, "weight EMA arena size");
+    TORCH_CHECK(ema_decay >= 0.0 && ema_decay < 1.0, "ema_decay must be in [0, 1), got ", ema_decay);
+    TORCH_CHECK(lz_hi <= lz_lo, "adamw: a lazy range cannot be combined with a weight EMA");
+    ep = ema->data_ptr<float>();
+  }
   adamw_launch(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), pb, n,
                sq.data_ptr<float>(), np, step.data_ptr<int64_t>(), hyper.data_ptr<float>(), (float)grad_scale,
-               cur_stream(), zero_hi, ld ? lz_lo : 0, ld ? lz_hi : 0, ld);
+               cur_stream(), zero_hi, ld ? lz_lo : 0, ld ? lz_hi : 0, ld, ep, (float)ema_decay, ema_warmup);
 }
 
 void advance_counters(Tensor step, Tensor rng, c10::optional<Tensor> sq) {
@@ -1327,7 +1335,7 @@ TORCH_LIBRARY(ddim_cold, m) {
   m.def("sqnorm(Tensor g, Tensor(a!) out, float scale, int lz_lo=0, int lz_hi=0) -> ()");
   m.def("adamw_step(Tensor(a!) p, Tensor(b!) g, Tensor(c!) m, Tensor(d!) v, Tensor(e!)? pbf, Tensor sq, "
         "Tensor step, Tensor hyper, float grad_scale, int zero_hi=-1, int lz_lo=0, int lz_hi=0, "
-        "Tensor(f!)? lazy_decay=None) -> ()");
+        "Tensor(f!)? lazy_decay=None, Tensor(g!)? ema=None, float ema_decay=0.0, bool ema_warmup=False) -> ()");
   m.def("advance_counters(Tensor(a!) step, Tensor(b!) rng, Tensor? sq) -> ()");
   m.def("ddim_step(Tensor x_t, Tensor x0_raw, Tensor coef) -> (Tensor, Tensor)");
   m.def("ddim_step_(Tensor(a!) x, Tensor x0_raw, Tensor(b!) x0_out, Tensor coef) -> ()");

@@ -280,9 +280,13 @@ void sqnorm_launch(const float* g, int64_t n, float* partials, int nparts, float
                    int64_t lz_lo = 0, int64_t lz_hi = 0);
 // zero_hi: zero the gradient arena only below this element (the part that is
 // accumulated into; everything above is overwritten by its producer next step)
+// ema: weight-EMA arena updated in the same pass, e <- p_new + d (e - p_new) with
+// d = ema_decay, or min(ema_decay, (1 + step[0]) / (10 + step[0])) with ema_warmup; not
+// together with a lazy range
 void adamw_launch(float* p, float* g, float* m, float* v, void* p_bf16, int64_t n, const float* sqnorm,
                   int nparts, const int64_t* step, const float* hyper, float grad_scale, hipStream_t stream,
-                  int64_t zero_hi = -1, int64_t lz_lo = 0, int64_t lz_hi = 0, float* lazy_decay = nullptr);
+                  int64_t zero_hi = -1, int64_t lz_lo = 0, int64_t lz_hi = 0, float* lazy_decay = nullptr,
+                  float* ema = nullptr, float ema_decay = 0.f, bool ema_warmup = false);
 void advance_counters_launch(int64_t* step, int64_t* rng, const float* sqnorm, int nparts, hipStream_t stream);
 
 // Diffusion / data (diffusion.hip)

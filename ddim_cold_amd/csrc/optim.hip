@@ -78,15 +78,40 @@ __device__ __forceinline__ void adamw_elem(float& p, float g, float& m, float& v
   p -= step_size * m / (sqrtf(v) * inv_sbc2 + eps);
 }
 
+// weight EMA, e <- p_new + d (e - p_new): three separately rounded fp32 operations (no
+// FMA contraction), so the result is reproducible on raw bits from p_new and e.
+// The contraction is switched off by pragma, on plain operators: hipcc's
+// __fmul_rn / __fadd_rn are plain `*` / `+` compiled under the default -ffp-contract,
+// and once inlined the product and the sum were fused into one v_fma_f32 (seen on
+// gfx950: last-bit differences from the three-operation result).
+__device__ __forceinline__ float ema_elem(float e, float p, float d) {
+#pragma clang fp contract(off)
+  const float diff = e - p;
+  const float scaled = d * diff;
+  return p + scaled;
+}
+
+// The updated parameters reach the EMA through an empty asm (no instruction): to the
+// compiler they are new values, so the EMA's arithmetic cannot take part in how the
+// AdamW expressions above it are vectorised and contracted.  Without it the two
+// instantiations rounded p differently in the scalar tail (other FMA choices).
+__device__ __forceinline__ void ema_fence(float& x) { asm volatile("" : "+v"(x)); }
+
 // hyper = {base_lr, beta1, beta2, eps, weight_decay, max_norm, T_max, eta_min}
 // step  = {adam_step, sched_step}
+// EMA: a fifth arena `ema` follows the updated parameters in the same pass (read + write,
+// 8 B per parameter more); ema_warmup ramps the decay as min(ema_decay, (1 + t) / (10 + t))
+// over the Adam steps t done before this one.  A skipped step leaves it alone.  The
+// EMA = false instantiation ignores the three trailing arguments.
+template <bool EMA>
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
                                                     float* __restrict__ v, bf16* __restrict__ pb, int64_t n,
                                                     const float* __restrict__ sqnorm, int nparts,
                                                     const int64_t* __restrict__ step,
                                                     const float* __restrict__ hyper, float grad_scale, bool vec,
                                                     int64_t zero_hi, int64_t lo4, int64_t len4,
-                                                    float* __restrict__ lazy_decay) {
+                                                    float* __restrict__ lazy_decay, float* __restrict__ ema,
+                                                    float ema_decay, int ema_warmup) {
   const float sq = sum_parts(sqnorm, nparts);
   const bool skip = !isfinite(sq);
   const float base_lr = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3], wd = hyper[4];
@@ -101,6 +126,11 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float
   const float step_size = lr / bc1;
   const float inv_sbc2 = 1.f / sqrtf(bc2);
   const float decay = 1.f - lr * wd;
+  float d = 0.f;
+  if constexpr (EMA) {
+    const float ts = (float)step[0];
+    d = ema_warmup ? fminf(ema_decay, __fdiv_rn(1.f + ts, 10.f + ts)) : ema_decay;
+  }
   if (len4 > 0 && !skip && blockIdx.x == 0 && threadIdx.x == 0) lazy_decay[0] *= decay;
   // 16-byte vectors (the arenas are allocator-aligned; `vec` is checked on the host),
   // scalar tail.  Same math per element as the scalar path.
@@ -126,6 +156,15 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float
       o[0] = f2bf(pv.x); o[1] = f2bf(pv.y); o[2] = f2bf(pv.z); o[3] = f2bf(pv.w);
       reinterpret_cast<bf16x4*>(pb)[i] = o;
     }
+    if constexpr (EMA) {
+      ema_fence(pv.x); ema_fence(pv.y); ema_fence(pv.z); ema_fence(pv.w);
+      float4 ev = reinterpret_cast<const float4*>(ema)[i];
+      ev.x = ema_elem(ev.x, pv.x, d);
+      ev.y = ema_elem(ev.y, pv.y, d);
+      ev.z = ema_elem(ev.z, pv.z, d);
+      ev.w = ema_elem(ev.w, pv.w, d);
+      reinterpret_cast<float4*>(ema)[i] = ev;
+    }
   }
   for (int64_t i = nv * 4 + (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
     float gi = g[i];
@@ -137,6 +176,10 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float
     v[i] = vi;
     p[i] = pi;
     if (pb) pb[i] = f2bf(pi);
+    if constexpr (EMA) {
+      ema_fence(pi);
+      ema[i] = ema_elem(ema[i], pi, d);
+    }
   }
 }
 
@@ -175,17 +218,20 @@ void sqnorm_launch(const float* g, int64_t n, float* out, int nparts, float scal
 
 void adamw_launch(float* p, float* g, float* m, float* v, void* p_bf16, int64_t n, const float* sqnorm,
                   int nparts, const int64_t* step, const float* hyper, float grad_scale, hipStream_t stream, int64_t zero_hi,
-                  int64_t lz_lo, int64_t lz_hi, float* lazy_decay) {
+                  int64_t lz_lo, int64_t lz_hi, float* lazy_decay, float* ema, float ema_decay, bool ema_warmup) {
   if (zero_hi < 0 || zero_hi > n) zero_hi = n;
   zero_hi = (zero_hi + 3) / 4 * 4 <= n ? (zero_hi + 3) / 4 * 4 : n;  // whole 16-B vectors
   auto al = [](const void* q, uintptr_t a) { return (reinterpret_cast<uintptr_t>(q) & (a - 1)) == 0; };
-  const bool vec = al(p, 16) && al(g, 16) && al(m, 16) && al(v, 16) && (p_bf16 == nullptr || al(p_bf16, 8));
+  const bool vec = al(p, 16) && al(g, 16) && al(m, 16) && al(v, 16) && (p_bf16 == nullptr || al(p_bf16, 8)) &&
+                   (ema == nullptr || al(ema, 16));
   check_lazy(n, lz_lo, lz_hi);
   int64_t len4 = lz_hi > lz_lo ? (lz_hi - lz_lo) / 4 : 0;
   if (!vec || lazy_decay == nullptr) len4 = 0;
-  hipLaunchKernelGGL(adamw_kernel, dim3(opt_grid(n - 4 * len4)), dim3(256), 0, stream, p, g, m, v,
+  if (ema != nullptr && len4 > 0) throw std::runtime_error("adamw: a lazy range cannot be combined with a weight EMA");
+  auto kern = ema != nullptr ? adamw_kernel<true> : adamw_kernel<false>;
+  hipLaunchKernelGGL(kern, dim3(opt_grid(n - 4 * len4)), dim3(256), 0, stream, p, g, m, v,
                      reinterpret_cast<bf16*>(p_bf16), n, sqnorm, nparts, step, hyper, grad_scale, vec, zero_hi, lz_lo / 4,
-                     len4, lazy_decay);
+                     len4, lazy_decay, ema, ema_decay, ema_warmup ? 1 : 0);
 }
 
 void advance_counters_launch(int64_t* step, int64_t* rng, const float* sqnorm, int nparts, hipStream_t stream) {

@@ -21,7 +21,7 @@ __all__ = [
     "native_available", "patch_embed_fwd", "layernorm_fwd", "qkv_fwd", "attn_fwd", "attn_keep_buffer",
     "linear_residual_fwd", "linear_gelu_fwd", "head_fwd", "smooth_l1_fwd_bwd", "img_to_tokgrad",
     "linear_dgrad", "linear_dgrad_gelu", "linear_wgrad", "layernorm_bwd", "attn_bwd", "embed_bwd",
-    "sqnorm", "adamw_step", "advance_counters", "ddim_step", "ddim_step_", "randn_", "q_sample",
+    "sqnorm", "adamw_step", "weight_ema_decay", "advance_counters", "ddim_step", "ddim_step_", "randn_", "q_sample",
     "pixelate_pair", "cold_batch", "gauss_batch", "head_step_rows_", "cold_step_", "cold_step_rows_",
     "image_to_rows", "rows_to_image", "embed_weight_rows", "patch_embed_cold_fwd", "ln_fold_",
 ]
@@ -535,18 +535,44 @@ def sqnorm(g, out, scale: float = 1.0, lazy=None):
     out[0] = (g.float() * scale).pow(2).sum()
 
 
+def weight_ema_decay(decay: float, t: int, warmup: bool) -> torch.Tensor:
+    """The weight EMA's decay for the update that follows ``t`` completed Adam steps, as
+    a fp32 scalar: ``decay``, or with ``warmup`` min(decay, (1 + t) / (10 + t)) evaluated
+    in fp32 (0.1 at the first update; what the kernel computes from ``step[0]``)."""
+    d = torch.tensor(float(decay), dtype=torch.float32)
+    if not warmup:
+        return d
+    ts = torch.tensor(int(t), dtype=torch.int64).to(torch.float32)
+    return torch.minimum(d, (1.0 + ts) / (10.0 + ts))
+
+
 def adamw_step(p, g, m, v, pbf, sq, step, hyper, grad_scale: float = 1.0, zero_hi: Optional[int] = None,
-               lazy=None, lazy_decay=None):
+               lazy=None, lazy_decay=None, ema=None, ema_decay: float = 0.0, ema_warmup: bool = False):
     """Fused AdamW over a flat arena (see csrc/optim.hip for the exact math).
     ``zero_hi``: zero the gradients only below this element (the producers of the
     rest overwrite them next step); default: all.  ``lazy`` = (lo, hi) with
     ``lazy_decay`` (fp32 [1]): parameters whose gradient and moments are identically
     zero; they are not touched, their weight decay (1 - lr*wd per step) accumulates
-    into ``lazy_decay`` for ``TrainEngine.materialize_lazy``."""
+    into ``lazy_decay`` for ``TrainEngine.materialize_lazy``.
+    ``ema`` (fp32, the arena's size): an exponential moving average of the parameters
+    updated in the same pass, ``e <- p_new + d * (e - p_new)`` as three separately rounded
+    fp32 operations, with ``d`` = :func:`weight_ema_decay` (``ema_decay``, ``step[0]``,
+    ``ema_warmup``); left alone on a skipped step; not together with ``lazy``."""
     lo, hi = lazy if lazy is not None and lazy_decay is not None else (0, 0)
     if _hip(p):
+        if ema is None:
+            return _ops().adamw_step(p, g, m, v, pbf, sq, step, hyper, float(grad_scale),
+                                     -1 if zero_hi is None else int(zero_hi), int(lo), int(hi), lazy_decay)
         return _ops().adamw_step(p, g, m, v, pbf, sq, step, hyper, float(grad_scale),
-                                 -1 if zero_hi is None else int(zero_hi), int(lo), int(hi), lazy_decay)
+                                 -1 if zero_hi is None else int(zero_hi), int(lo), int(hi), lazy_decay,
+                                 ema, float(ema_decay), bool(ema_warmup))
+    if ema is not None:
+        if hi > lo:
+            raise RuntimeError("adamw_step: a lazy range cannot be combined with a weight EMA")
+        if ema.dtype != torch.float32 or ema.numel() != p.numel():
+            raise RuntimeError("adamw_step: ema must be fp32 of the arena's size")
+        if not 0.0 <= float(ema_decay) < 1.0:
+            raise RuntimeError(f"adamw_step: ema_decay must be in [0, 1), got {ema_decay}")
     import math
     sqv = float(sq.sum())
     base_lr, b1, b2, eps, wd, max_norm, tmax, eta_min = (float(x) for x in hyper.tolist()[:8])
@@ -573,6 +599,9 @@ def adamw_step(p, g, m, v, pbf, sq, step, hyper, grad_scale: float = 1.0, zero_h
         p[lo:hi], m[lo:hi], v[lo:hi] = keep
     if pbf is not None:
         pbf.copy_(p.to(torch.bfloat16))
+    if ema is not None:  # e <- p + d (e - p): sub, mul, add, each rounded to fp32
+        d = weight_ema_decay(ema_decay, t - 1, ema_warmup).to(p.device)
+        ema.sub_(p).mul_(d).add_(p)
 
 
 def advance_counters(step, rng, sq=None):

@@ -14,6 +14,14 @@ reference): ``'rng'`` (device RNG seed/step; a resume restores only the
 step, each rank keeps its own seed), ``'engine_steps'``, ``'scaler'`` (GradScaler
 layout, scale 1: bf16 training needs no loss scaling).
 
+Runs that keep a weight EMA (``weight_ema`` > 0) add two more keys to
+``lastepoch.pkl``: ``'ema_state_dict'`` (the EMA weights, ``module.``-prefixed names
+exactly like ``'state_dict'``) and ``'ema'`` (``{'decay': float, 'warmup': bool}``), and
+write ``bestloss_ema.pkl`` (plain un-prefixed ``state_dict`` of the EMA weights) next to
+``bestloss.pkl`` whenever that one is written.  Without an EMA neither key nor file
+appears.  A resume restores the EMA from the key (missing: it restarts from the loaded
+weights, with a warning; present but EMA off: ignored).
+
 Loading uses ``weights_only=True`` (no arbitrary unpickling).
 """
 from __future__ import annotations
@@ -50,9 +58,36 @@ def save_weights(model, path: str):
     _atomic_save(cpu_state_dict(model), path)
 
 
-def load_weights(model, path: str, strict: bool = True):
+def ema_path(path: str) -> str:
+    """``<name>_ema<.ext>`` next to ``path`` (``bestloss.pkl`` -> ``bestloss_ema.pkl``)."""
+    stem, ext = os.path.splitext(path)
+    return stem + "_ema" + ext
+
+
+def resolve_ema_checkpoint(path: str):
+    """Where the EMA weights of ``path`` live, for the sampling CLIs' ``--ema``:
+    ``(path, True)`` if it is a ``lastepoch.pkl``-style file with ``'ema_state_dict'``,
+    else ``(<path>_ema sibling, False)``.  ``FileNotFoundError`` naming the path looked
+    for when neither exists."""
+    if os.path.isfile(path):
+        sd = torch.load(path, map_location="cpu", weights_only=True)
+        if isinstance(sd, dict) and "ema_state_dict" in sd:
+            return path, True
+    sib = ema_path(path)
+    if os.path.isfile(sib):
+        return sib, False
+    raise FileNotFoundError(f"--ema: no 'ema_state_dict' in {path} and no EMA weights file at {sib}")
+
+
+def load_weights(model, path: str, strict: bool = True, ema: bool = False):
+    """Load a plain ``state_dict`` file, or the ``'state_dict'`` of a
+    ``lastepoch.pkl``-style dict (``ema``: its ``'ema_state_dict'`` instead)."""
     sd = torch.load(path, map_location="cpu", weights_only=True)
-    if isinstance(sd, dict) and "state_dict" in sd and not any(torch.is_tensor(v) for v in sd.values()):
+    if ema:
+        if not (isinstance(sd, dict) and "ema_state_dict" in sd):
+            raise KeyError(f"{path} has no 'ema_state_dict' (not a lastepoch.pkl of a run with weight_ema > 0)")
+        sd = sd["ema_state_dict"]
+    elif isinstance(sd, dict) and "state_dict" in sd and not any(torch.is_tensor(v) for v in sd.values()):
         sd = sd["state_dict"]
     sd = strip_prefix(sd)
     missing, unexpected = model.load_state_dict(sd, strict=strict)
@@ -66,7 +101,7 @@ def lastepoch_dict(snap, epoch: int, steps: int, loss_rec: float, metric: float)
     """The reference's ``lastepoch.pkl`` dict (multi_gpu_trainer.py:155-163) from a
     host snapshot of the engine (``TrainEngine.snapshot_to_host``)."""
     snap.wait()
-    return {
+    d = {
         "epoch": int(epoch),
         "steps": int(steps),
         "loss_rec": float(loss_rec),
@@ -81,6 +116,10 @@ def lastepoch_dict(snap, epoch: int, steps: int, loss_rec: float, metric: float)
         "scaler": {"scale": 1.0, "growth_factor": 2.0, "backoff_factor": 0.5, "growth_interval": 2000,
                    "_growth_tracker": 0},
     }
+    if getattr(snap, "ema", None) is not None:
+        d["ema_state_dict"] = add_prefix(snap.ema_state_dict())
+        d["ema"] = {"decay": float(snap.engine.cfg.weight_ema), "warmup": bool(snap.engine.cfg.weight_ema_warmup)}
+    return d
 
 
 def save_lastepoch(path: str, model, engine, epoch: int, steps: int, loss_rec: float, metric: float):
@@ -134,6 +173,8 @@ class CheckpointWriter:
                 t2 = time.perf_counter()
                 if best_path is not None:
                     _atomic_save(strip_prefix(d["state_dict"]), best_path)
+                    if "ema_state_dict" in d:
+                        _atomic_save(strip_prefix(d["ema_state_dict"]), ema_path(best_path))
                 _atomic_save(d, lastepoch_path)
                 t3 = time.perf_counter()
                 self.last_write_s = t3 - t0
@@ -167,6 +208,12 @@ def load_lastepoch(path: str, model, engine) -> dict:
             # rank keeps its own seed (cfg.seed * 1000 + rank) so the ranks' cold
             # timesteps / dropout masks stay independent after a resume
             engine.rng[1:].copy_(ckpt["rng"][1:].to(engine.rng.device))
+        if getattr(engine, "flat_e", None) is not None:
+            if ckpt.get("ema_state_dict") is not None:
+                engine.load_ema_state_dict(strip_prefix(ckpt["ema_state_dict"]))
+            else:  # sync_params_from_model() above already reset it to the loaded weights
+                import warnings
+                warnings.warn(f"{path} has no 'ema_state_dict': the weight EMA starts from the loaded weights")
     return ckpt
 
 

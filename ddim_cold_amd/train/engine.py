@@ -40,6 +40,7 @@ AdamW step, cosine LR step, zero_grad) re-designed for a latency-bound
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import copy
 import os
@@ -199,6 +200,19 @@ class EngineConfig:
     # (~8 us before each step's first kernel in the graph-mode trace) is paid once
     # per K steps.  train_step() keeps replaying the one-step graph.
     graph_steps: int = 1
+    # exponential moving average of the WEIGHTS (not the loss: that is ema_decay above):
+    # 0 = off, else the decay d of e <- p + d (e - p), kept in one more fp32 arena that the
+    # optimizer launch updates in the same pass (no extra launch, no communication: data
+    # parallel replicas are bit-identical and so are their EMAs).  Read it with
+    # ema_state_dict(), evaluate / sample on it inside ``with engine.ema_weights():``.
+    # With it on, the lazy time-embedding range is off: those rows go through the
+    # optimizer pass every step, as torch.optim.AdamW would update them, so that their
+    # EMA follows them (~11 % of the ViT-tiny arena back in the pass).
+    weight_ema: float = 0.0
+    # ramp the decay as min(weight_ema, (1 + t) / (10 + t)) over the Adam steps t done so
+    # far (0.1 at the first update), so the average forgets the initial weights quickly;
+    # a resume continues the ramp from the restored Adam step
+    weight_ema_warmup: bool = True
 
 
 def _align(n: int) -> int:
@@ -218,6 +232,8 @@ class TrainEngine:
         self.rank = dist.get_rank(process_group) if self.dist_on else 0
         self.segmented = self.world > 1 or cfg.force_segments
         self.is_cuda = self.device.type == "cuda"
+        if not 0.0 <= float(cfg.weight_ema) < 1.0:
+            raise ValueError(f"weight_ema must be in [0, 1), got {cfg.weight_ema!r}")
         self._build_arenas()
         dev = self.device
         self.rng = torch.tensor([cfg.seed, 0], dtype=torch.int64, device=dev)
@@ -273,6 +289,14 @@ class TrainEngine:
             else:
                 dist.broadcast(self.flat_p, src=0, group=self.pg)
             self._refresh_shadow()
+        # weight EMA arena: a copy of the final (loaded, broadcast) parameters; the frozen
+        # tail past train_hi is never updated and just stays equal to them
+        self.flat_e = self.opt_e = None
+        self._ema_tmp = None      # ema_weights(): the swap's reusable temp arena
+        self._ema_scope = False   # inside ema_weights(): flat_p holds the EMA
+        if cfg.weight_ema > 0:
+            self.flat_e = self.flat_p.clone()
+            self.opt_e = self.flat_e[:self.train_hi]
         model._engine = self
 
     def _comm_stream(self):
@@ -505,8 +529,9 @@ class TrainEngine:
         self.lazy_decay = torch.ones(1, dtype=torch.float32, device=self.device)
         self._lazy_dirty = False
         rows = self.cfg.temb_rows
+        # (off with a weight EMA: the EMA of those rows has to follow them every step)
         if (rows is not None and 0 < rows < c.total_steps and "time_embed.weight" in self.offsets
-                and "time_embed.weight" not in self.frozen):
+                and "time_embed.weight" not in self.frozen and not self.cfg.weight_ema > 0):
             to, tn = self.offsets["time_embed.weight"]
             lo, hi = (to + rows * c.dim + 3) // 4 * 4, (to + tn) // 4 * 4
             if hi > lo and hi <= self.train_hi:
@@ -737,9 +762,11 @@ class TrainEngine:
             ops.sqnorm(self.opt_g, self.sqnorm, gs, lazy=self.lazy)
         if loss_acc is not None:
             loss_parts = loss_acc
+        ema = {} if self.opt_e is None else dict(ema=self.opt_e, ema_decay=self.cfg.weight_ema,
+                                                 ema_warmup=self.cfg.weight_ema_warmup)
         ops.adamw_step(self.opt_p, self.opt_g, self.opt_m, self.opt_v, self.opt_pb, self.sqnorm,
                        self.step_ctr, self.hyper, gs, zero_hi=self.acc_hi if overwrite else None,
-                       lazy=self.lazy, lazy_decay=self.lazy_decay)
+                       lazy=self.lazy, lazy_decay=self.lazy_decay, **ema)
         if self.wt is not None:  # the input-gradient GEMMs' transposed shadows of the new weights
             self.wt.refresh()
         if tail:
@@ -1012,6 +1039,8 @@ class TrainEngine:
     def _snapshot_state(self):
         self.materialize_lazy()
         keys = ("flat_p", "flat_g", "flat_m", "flat_v", "rng", "step_ctr", "loss_ema", "loss_last", "lazy_decay")
+        if self.flat_e is not None:
+            keys += ("flat_e",)
         return {k: getattr(self, k).clone() for k in keys}, self.steps_done
 
     def _restore_state(self, snap):
@@ -1308,6 +1337,7 @@ class TrainEngine:
         ``materialize``: apply the lazily accumulated weight decay afterwards (see
         ``lazy``), so every parameter is current when the call returns.
         Returns the device loss tensor of the last step (no host sync)."""
+        self._no_ema_scope("train_steps")
         done = 0
         while done < n:
             multi = self._multi
@@ -1340,6 +1370,7 @@ class TrainEngine:
         epoch end, where it evaluates and checkpoints).
 
         Returns the device loss tensor (no host sync)."""
+        self._no_ema_scope("train_step")
         if self.batch_fn is None:
             raise RuntimeError("set_batch_fn() or use step(x, target, t)")
         use_graph = self.cfg.use_graph and self.is_cuda
@@ -1358,6 +1389,7 @@ class TrainEngine:
 
     def step(self, x_t: torch.Tensor, target: torch.Tensor, t: torch.Tensor):
         """Convenience: copy an externally produced batch into static buffers and step."""
+        self._no_ema_scope("step")
         if self._static is None or self._static[0].shape != x_t.shape:
             self._static = (torch.empty_like(x_t, device=self.device), torch.empty_like(target, device=self.device),
                             torch.empty(t.shape, dtype=torch.int64, device=self.device))
@@ -1368,6 +1400,70 @@ class TrainEngine:
         sy.copy_(target, non_blocking=True)
         st_.copy_(t, non_blocking=True)
         return self.train_step()
+
+    # ------------------------------------------------------------------ weight EMA
+    def _no_ema_scope(self, what: str):
+        if self._ema_scope:
+            raise RuntimeError(f"{what}() inside ema_weights(): the parameter arena holds the EMA weights; "
+                               "leave the scope before training")
+
+    def _need_ema(self, what: str):
+        if self.flat_e is None:
+            raise RuntimeError(f"{what}: this engine keeps no weight EMA (EngineConfig.weight_ema is 0)")
+
+    def _swap_ema(self):
+        """Exchange the contents of the parameter and EMA arenas (no address changes, so
+        every captured graph stays valid) and re-derive what the kernels read."""
+        if self._ema_tmp is None:
+            self._ema_tmp = torch.empty_like(self.flat_p)
+        self._ema_tmp.copy_(self.flat_p)
+        self.flat_p.copy_(self.flat_e)
+        self.flat_e.copy_(self._ema_tmp)
+        self._refresh_shadow()
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Scope in which the model runs on its EMA weights: ``model``,
+        ``param_tensors``, ``trainer.evaluate`` and every sampler see them (bf16 shadow,
+        LayerNorm fold and transposed shadows re-derived); on exit the arenas are
+        swapped back, bitwise what they were.  Training inside the scope raises; the
+        scope is not re-entrant."""
+        self._need_ema("ema_weights()")
+        if self._ema_scope:
+            raise RuntimeError("ema_weights() is not re-entrant")
+        self._swap_ema()
+        self._ema_scope = True
+        try:
+            yield self
+        finally:
+            self._swap_ema()
+            self._ema_scope = False
+
+    def _arena_state_dict(self, flat: torch.Tensor) -> Dict[str, torch.Tensor]:
+        """The model's ``state_dict`` (keys, shapes, order) read from an arena."""
+        shapes = {n: p.shape for n, p in self.model.named_parameters()}
+        out = {}
+        for n in self.model.state_dict().keys():
+            if n not in self.offsets:
+                raise KeyError(f"{n}: not in the parameter arena (a buffer?)")
+            o, k = self.offsets[n]
+            out[n] = flat[o:o + k].view(shapes[n]).clone()
+        return out
+
+    def ema_state_dict(self) -> Dict[str, torch.Tensor]:
+        """The EMA weights as the model's ``state_dict`` (keys, shapes, order)."""
+        self._need_ema("ema_state_dict()")
+        return self._arena_state_dict(self.flat_p if self._ema_scope else self.flat_e)
+
+    def load_ema_state_dict(self, sd: Dict[str, torch.Tensor]):
+        """Restore the EMA arena from a ``state_dict`` of the model's keys (strict)."""
+        self._need_ema("load_ema_state_dict()")
+        self._no_ema_scope("load_ema_state_dict")
+        if set(sd) != set(self.offsets):
+            raise KeyError(f"EMA state dict keys differ from the model's: missing "
+                           f"{sorted(set(self.offsets) - set(sd))}, unexpected {sorted(set(sd) - set(self.offsets))}")
+        for n, (o, k) in self.offsets.items():
+            self.flat_e[o:o + k].copy_(sd[n].reshape(-1).to(self.device, torch.float32))
 
     # ------------------------------------------------------------------ state
     def current_lr(self) -> float:
@@ -1417,14 +1513,18 @@ class TrainEngine:
         cur = torch.cuda.current_stream(self.device) if self.is_cuda else None
         if self._snap is None:
             pin = self.is_cuda
-            host = [torch.empty(t.shape, dtype=t.dtype, pin_memory=pin)
-                    for t in (self.flat_p, self.flat_m, self.flat_v, self.step_ctr, self.rng)]
-            dev = [torch.empty_like(t) for t in (self.flat_p, self.flat_m, self.flat_v, self.step_ctr, self.rng)] \
-                if self.is_cuda else None
+            like = (self.flat_p, self.flat_m, self.flat_v, self.step_ctr, self.rng)
+            if self.flat_e is not None:  # the weight EMA rides along as a sixth buffer
+                like += (self.flat_e,)
+            host = [torch.empty(t.shape, dtype=t.dtype, pin_memory=pin) for t in like]
+            dev = [torch.empty_like(t) for t in like] if self.is_cuda else None
             side = torch.cuda.Stream(self.device) if self.is_cuda else None
             self._snap = (host, dev, side)
         host, dev, side = self._snap
         src = (self.flat_p, self.flat_m, self.flat_v, self.step_ctr, self.rng)
+        if self.flat_e is not None:
+            self._no_ema_scope("snapshot_to_host")
+            src += (self.flat_e,)
         ev = None
         if self.is_cuda:
             for d, t in zip(dev, src):
@@ -1438,7 +1538,7 @@ class TrainEngine:
         else:
             for h, t in zip(host, src):
                 h.copy_(t)
-        return HostSnapshot(self, *host, ev, int(self.steps_done))
+        return HostSnapshot(self, *host[:5], ev, int(self.steps_done), ema=host[5] if len(host) > 5 else None)
 
     def load_optimizer_state_dict(self, sd: dict):
         st = sd.get("state", {})
@@ -1495,10 +1595,16 @@ class TrainEngine:
         """Call after loading weights into ``model`` (its params are arena views)."""
         self.lazy_decay.fill_(1.0)  # the loaded values are current: no decay pending
         self._lazy_dirty = False
+        if self.flat_e is not None:  # the EMA restarts from the loaded weights
+            self._no_ema_scope("sync_params_from_model")
+            self.flat_e.copy_(self.flat_p)
         self._refresh_shadow()
 
     def detach(self):
-        """Release the model from the engine (params stay on the device, as plain tensors)."""
+        """Release the model from the engine (params stay on the device, as plain tensors).
+        The EMA arena stays readable (``ema_state_dict``); the swap's temp arena is freed."""
+        self._no_ema_scope("detach")
+        self._ema_tmp = None
         self.materialize_lazy()
         for n, p in self.model.named_parameters():
             p.data = p.data.clone()
@@ -1511,8 +1617,9 @@ class HostSnapshot:
     fp32 parameter / moment arenas, counters and RNG state, plus what is needed to
     lay them out as the reference's checkpoint dicts without touching the device."""
 
-    def __init__(self, engine: TrainEngine, p, m, v, step_ctr, rng, event, steps_done: int):
+    def __init__(self, engine: TrainEngine, p, m, v, step_ctr, rng, event, steps_done: int, ema=None):
         self.engine, self.p, self.m, self.v, self.step_ctr, self.rng = engine, p, m, v, step_ctr, rng
+        self.ema = ema  # host copy of the weight EMA arena; None when the engine keeps none
         self.event = event
         self.steps_done = steps_done
 
@@ -1531,6 +1638,12 @@ class HostSnapshot:
             o, k = eng.offsets[n]
             out[n] = self.p[o:o + k].view(shapes[n]).clone()
         return out
+
+    def ema_state_dict(self) -> Dict[str, torch.Tensor]:
+        """The EMA weights as the model's ``state_dict``, from the snapshot."""
+        if self.ema is None:
+            raise RuntimeError("this snapshot holds no weight EMA (EngineConfig.weight_ema is 0)")
+        return self.engine._arena_state_dict(self.ema)
 
     def optimizer_state_dict(self) -> dict:
         return self.engine._optimizer_sd(self.m, self.v, int(self.step_ctr[0]), int(self.step_ctr[1]))

@@ -11,7 +11,8 @@ Reference flow (multi_gpu_trainer.py:47-165) reproduced:
 * every ``log_every`` (100) steps: ``steps: .. loss: .. time_cost: ..`` (rank 0),
 * per epoch: eval mean smooth-L1 over the val shard, SUM-all-reduced / world,
   ``epoch: .. loss: ..``, scalar ``loss``, ``bestloss.pkl`` on improvement and
-  ``lastepoch.pkl`` every epoch (rank 0),
+  ``lastepoch.pkl`` every epoch (rank 0); with ``weight_ema`` the EMA weights ride in
+  both (``'ema_state_dict'``, ``bestloss_ema.pkl``) and ``ema_eval`` validates on them,
 * resume from ``resume:`` (epoch+1, loss_rec, steps, best metric, optimizer,
   scheduler).
 
@@ -22,6 +23,7 @@ runs as replayed hipGraphs, and the loss is read back only at log points
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import os
 import shutil
@@ -238,7 +240,8 @@ def train_worker(rank: int, world: int, cfg: ExperimentConfig, exp_name: str, pa
     temb_rows = int(math.log2(cfg.image_size[1])) + 1 if cfg.dataset.startswith("cold") else None
     ecfg = EngineConfig(lr=cfg.lr, t_max=steps_per_epoch * cfg.epoch[1], use_graph=cfg.graph,
                         bucket_blocks=cfg.bucket_blocks, seed=cfg.seed * 1000 + rank, temb_rows=temb_rows,
-                        grad_accum=A, force_segments=cfg.force_segments, graph_steps=cfg.graph_steps)
+                        grad_accum=A, force_segments=cfg.force_segments, graph_steps=cfg.graph_steps,
+                        weight_ema=cfg.weight_ema, weight_ema_warmup=cfg.weight_ema_warmup)
     engine = TrainEngine(model, ecfg, device=device)
     # the epoch's DistributedSampler table [steps, micro-batch, B] lives on the device
     # (refilled once per epoch); the batch draw reads row ``scheduler step %
@@ -350,7 +353,8 @@ def train_worker(rank: int, world: int, cfg: ExperimentConfig, exp_name: str, pa
                 model.eval()
                 vidx = shard_indices(n_val, world, rank, epoch, cfg.seed, shuffle=False, drop_last=False)
                 eval_rng[1] = epoch * val_batches
-                with phase("evaluate"):
+                # ema_eval: the metric (and so the bestloss decision) is that of the EMA weights
+                with phase("evaluate"), (engine.ema_weights() if cfg.ema_eval else contextlib.nullcontext()):
                     vloss = evaluate(model, engine, val_pool, vidx, B, cfg.dataset, cfg.model_total_steps, eval_rng)
                 vloss = pdist.all_reduce_mean(vloss, device)
                 model.train()

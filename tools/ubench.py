@@ -86,6 +86,9 @@ def main():
     hy = torch.tensor([1e-4, 0.9, 0.999, 1e-8, 0.05, 1.0, 1000.0, 0.0], device=dev)
     res["sqnorm 7.3M"] = t(lambda: ops.sqnorm(g_, sq, 1.0))
     res["adamw 7.3M"] = t(lambda: ops.adamw_step(p_, g_, m_, v_, pb, sq, st, hy, 1.0))
+    e_ = p_.clone()  # the weight EMA arena updated by the same pass (+8 B per parameter)
+    res["adamw+ema 7.3M"] = t(lambda: ops.adamw_step(p_, g_, m_, v_, pb, sq, st, hy, 1.0, ema=e_, ema_decay=0.9999,
+                                                      ema_warmup=True))
     res["empty kernel (torch fill 1 elem)"] = t(lambda: sq.zero_())
     for k, v in res.items():
         print(f"{v:8.2f} us  {k}")
