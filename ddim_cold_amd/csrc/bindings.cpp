@@ -13,8 +13,6 @@
 #include "kernels.h"
 #include <algorithm>
 #include <cstdlib>
-#include <map>
-#include <mutex>
 
 using at::Tensor;
 
@@ -612,10 +610,6 @@ void linear_wgrad(Tensor dy, Tensor x, Tensor dw, c10::optional<Tensor> db) {
   gemm_wgrad(g, splits, cur_stream());
 }
 
-// Grouped weight gradients: one launch for all (dy_i, x_i) -> dW_i += dy_i^T x_i
-// (db_i += colsum dy_i).  The token reduction is split over fp32 atomics (2-way
-// for a full block group, more for small groups); splits == 1 would use a plain
-// read-add-write epilogue.
 // grad-norm partial buffers: every partial is written (sqnorm: one block each; the
 // fused weight-gradient launch: tiles + tail, rest zeroed) and summed by consumers
 int check_parts(const Tensor& t, const char* who) {
@@ -626,21 +620,20 @@ int check_parts(const Tensor& t, const char* who) {
 
 static std::vector<GemmArgs> wgrad_probs(const std::vector<Tensor>& dys, const std::vector<Tensor>& xs,
                                          const std::vector<Tensor>& dws,
-                                         const std::vector<c10::optional<Tensor>>& dbs, int* tiles_out,
-                                         int* min_kt_out) {
+                                         const std::vector<c10::optional<Tensor>>& dbs) {
   const size_t n = dys.size();
-  TORCH_CHECK(xs.size() == n && dws.size() == n && dbs.size() == n, "wgrad_group: list sizes");
+  TORCH_CHECK(n > 0 && xs.size() == n && dws.size() == n && dbs.size() == n,
+              "wgrad_multi: one dy, x, dw, db per problem");
   std::vector<GemmArgs> probs;
-  int tiles = 0, min_kt = 1 << 30;
   for (size_t i = 0; i < n; ++i) {
     const Tensor &dy = dys[i], &x = xs[i], &dw = dws[i];
     CHECK_IN(dy, BF16); CHECK_IN(x, BF16); CHECK_IN(dw, F32);
     TORCH_CHECK(dy.device() == dys[0].device() && x.device() == dy.device() && dw.device() == dy.device(),
                 "wgrad_group: tensors on different devices");
-    TORCH_CHECK(dy.dim() == 2 && x.dim() == 2 && dy.size(0) == x.size(0), "wgrad_group shapes");
+    TORCH_CHECK(dy.dim() == 2 && x.dim() == 2 && dy.size(0) == x.size(0) && dy.size(0) > 0, "wgrad_group shapes");
     const int M = dy.size(0), Nout = dy.size(1), K = x.size(1);
     TORCH_CHECK(dw.numel() == (int64_t)Nout * K, "wgrad_group: dw shape");
-    TORCH_CHECK(Nout % 8 == 0 && K % 8 == 0, "wgrad dims must be multiples of 8");
+    TORCH_CHECK(Nout > 0 && K > 0 && Nout % 8 == 0 && K % 8 == 0, "wgrad dims must be multiples of 8");
     GemmArgs g;
     g.A = dy.data_ptr(); g.B = x.data_ptr();
     g.M = Nout; g.N = K; g.K = M; g.lda = Nout; g.ldb = K;
@@ -651,50 +644,44 @@ static std::vector<GemmArgs> wgrad_probs(const std::vector<Tensor>& dys, const s
       g.bias = dbs[i]->data_ptr<float>();
     }
     probs.push_back(g);
-    tiles += ((Nout + 63) / 64) * ((K + 63) / 64);
-    min_kt = std::min(min_kt, (M + 63) / 64);
   }
-  if (tiles_out) *tiles_out = tiles;
-  if (min_kt_out) *min_kt_out = min_kt;
   return probs;
 }
 
-// Tickets of the K-split weight-gradient tail: 4,096 ints per (device, stream), zeroed
-// once (the first call is an eager step, outside any graph); each split tile's last piece
-// resets its ticket, so every launch on that stream finds them zero (launches on one
-// stream run in order; two streams -- e.g. two engines in one process -- get their own).
-static int* split_tickets(const c10::Device& dev) {
-  static std::mutex mu;
-  static std::map<std::pair<int, int64_t>, Tensor> bufs;
-  const auto key = std::make_pair((int)dev.index(), (int64_t)c10::hip::getCurrentHIPStream(dev.index()).id());
-  std::lock_guard<std::mutex> lk(mu);
-  auto it = bufs.find(key);
-  if (it == bufs.end())
-    it = bufs.emplace(key, at::zeros({4096}, at::TensorOptions().dtype(at::kInt).device(dev))).first;
-  return it->second.data_ptr<int>();
+// the (Nout, K, tokens) of every problem, planned on the current device's CU count
+static WgradPlan wgrad_plan_of(const std::vector<WgradShape>& shapes) {
+  try {
+    return wgrad_plan(shapes, gemm_cu_count());
+  } catch (const std::invalid_argument& e) {
+    TORCH_CHECK(false, e.what());
+  }
 }
 
-// Every weight gradient of a training step in ONE launch (gemm_wgrad_multi_kernel)
+// Every weight gradient of a training step in ONE launch (gemm_wgrad_multi_kernel);
+// more than 32 problems: consecutive launches of <= 32 (csrc/wgrad_plan.h).
 // sq_parts / arena: also write the grad-norm partials of the whole gradient arena
-// (the launches must then be its last writers): the arena ranges outside every dW /
-// db target and outside the lazy range [lz_lo, lz_hi) go to the tail workgroups of
-// the last launch.  More than 32 problems: consecutive launches of <= 32, each
-// writing its tiles' partials after the previous launch's.
+// (the launches must then be its last writers): each launch writes its tiles' partials
+// after the previous launch's, and the arena ranges outside every dW / db target and
+// outside the lazy range [lz_lo, lz_hi) go to the tail workgroups of the last launch.
+// split_tickets: WGRAD_TICKETS zeroed ints for the K-split tail tiles of wide launches
+// (each tile's last piece resets its ticket, so launches ordered on one stream share one
+// buffer); without them an eager call zero-fills its own, a captured one is refused.
+// Validate, plan, launch: nothing is queued before every check has passed.
 void linear_wgrad_multi(std::vector<Tensor> dys, std::vector<Tensor> xs, std::vector<Tensor> dws,
                         std::vector<c10::optional<Tensor>> dbs, bool store, c10::optional<Tensor> sq_parts,
                         c10::optional<Tensor> arena, int64_t lz_lo, int64_t lz_hi, c10::optional<Tensor> emb_g,
                         c10::optional<Tensor> emb_t, c10::optional<Tensor> emb_rng, int64_t emb_site, double emb_p,
                         c10::optional<Tensor> emb_cls, c10::optional<Tensor> emb_pos, c10::optional<Tensor> emb_temb,
                         int64_t emb_owners, c10::optional<Tensor> ln_ws, c10::optional<Tensor> ln_ptrs,
-                        std::vector<int64_t> ln_offs, int64_t ln_C, int64_t ln_R, bool ln_store) {
-  TORCH_CHECK(!dys.empty() && dys.size() == xs.size() && dys.size() == dws.size() && dys.size() == dbs.size(),
-              "wgrad_multi: one dy, x, dw, db per problem");
+                        std::vector<int64_t> ln_offs, int64_t ln_C, int64_t ln_R, bool ln_store,
+                        c10::optional<Tensor> split_tickets) {
+  // ---- validate
+  const std::vector<GemmArgs> probs = wgrad_probs(dys, xs, dws, dbs);
   const c10::DeviceGuard guard(dys[0].device());
   const bool fused = sq_parts.has_value() && sq_parts->defined();
   // embedding gradients + LayerNorm finalize as extra workgroups (embed_parts.h)
   const bool with_emb = emb_g.has_value() && emb_g->defined();
   WgradEmbed we{};
-  std::vector<std::pair<int64_t, int64_t>> covered;  // arena ranges the embedding workgroups write
   if (with_emb) {
     const Tensor& g = *emb_g;
     CHECK_IN(g, F32); CHECK_IN((*emb_t), I64); check_rng(*emb_rng);
@@ -722,139 +709,126 @@ void linear_wgrad_multi(std::vector<Tensor> dys, std::vector<Tensor> xs, std::ve
       we.rf.store = ln_store ? 1 : 0;
     }
   }
-  WgradSq sq;
+  const bool have_tickets = split_tickets.has_value() && split_tickets->defined();
+  if (have_tickets) {
+    CHECK_IN((*split_tickets), at::kInt);
+    TORCH_CHECK(split_tickets->numel() >= WGRAD_TICKETS && split_tickets->device() == dys[0].device(),
+                "wgrad_multi: split_tickets must hold 4,096 ints on the operands' device (ops.wgrad_tickets)");
+  }
+  // element intervals inside the arena: the targets, and what the tail skips without a tile
+  // writing it -- the lazy range (zero forever) and the embedding workgroups' outputs (they
+  // write their own partials)
+  WgradRanges targets, skipped;
   int np = 0;
   if (fused) {
     TORCH_CHECK(arena.has_value() && arena->defined(), "wgrad_multi: grad-norm partials need the gradient arena");
     CHECK_IN((*sq_parts), F32); CHECK_IN((*arena), F32);
     np = check_parts(*sq_parts, "wgrad_multi");
     const float* base = arena->data_ptr<float>();
-    const int64_t n = arena->numel();
-    // element intervals of the targets inside the arena
-    std::vector<std::pair<int64_t, int64_t>> iv;
-    auto add = [&](const Tensor& t) {
+    auto add = [&](WgradRanges& to, const Tensor& t) {
       TORCH_CHECK(t.is_contiguous(), "wgrad_multi: grad-norm fusion needs contiguous targets");
       const int64_t off = t.data_ptr<float>() - base;
-      TORCH_CHECK(off >= 0 && off + t.numel() <= n, "wgrad_multi: a weight-gradient target lies outside the arena");
-      iv.emplace_back(off, off + t.numel());
+      to.emplace_back(off, off + t.numel());
     };
     for (size_t i = 0; i < dws.size(); ++i) {
-      add(dws[i]);
-      if (dbs[i].has_value() && dbs[i]->defined()) add(*dbs[i]);
+      add(targets, dws[i]);
+      if (dbs[i].has_value() && dbs[i]->defined()) add(targets, *dbs[i]);
     }
-    std::sort(iv.begin(), iv.end());
-    for (size_t i = 1; i < iv.size(); ++i)
-      TORCH_CHECK(iv[i].first >= iv[i - 1].second,
-                  "wgrad_multi: overlapping weight-gradient targets (the partials would count them twice)");
-    // ranges the tail skips without a tile writing them: the lazy range (zero forever)
-    // and the embedding workgroups' outputs (they write their own partials)
-    if (lz_hi > lz_lo) iv.emplace_back(lz_lo, lz_hi);
+    if (lz_hi > lz_lo) skipped.emplace_back(lz_lo, lz_hi);
     if (with_emb) {
-      auto cov = [&](const Tensor& t) {
-        const int64_t off = t.data_ptr<float>() - base;
-        TORCH_CHECK(off >= 0 && off + t.numel() <= n, "wgrad_multi: an embedding gradient lies outside the arena");
-        iv.emplace_back(off, off + t.numel());
-      };
-      cov(*emb_cls); cov(*emb_pos); cov(*emb_temb);
-      for (int64_t o : ln_offs) {
-        TORCH_CHECK(o >= 0 && o + ln_C <= n, "wgrad_multi: a LayerNorm gradient lies outside the arena");
-        iv.emplace_back(o, o + ln_C);
-      }
+      add(skipped, *emb_cls); add(skipped, *emb_pos); add(skipped, *emb_temb);
+      for (int64_t o : ln_offs) skipped.emplace_back(o, o + ln_C);
     }
-    std::sort(iv.begin(), iv.end());
-    sq.base = base;
-    int64_t cur = 0, rest = 0;
-    auto gap = [&](int64_t lo, int64_t hi) {
-      if (hi <= lo) return;
-      TORCH_CHECK(sq.nr < WSQ_MAX_RANGES, "wgrad_multi: more than 16 arena ranges outside the weight gradients");
+  }
+
+  // ---- plan
+  std::vector<WgradShape> shapes;
+  for (const GemmArgs& p : probs) shapes.push_back({p.M, p.N, p.K});
+  const WgradPlan plan = wgrad_plan_of(shapes);
+  const size_t nl = plan.launches.size();
+  WgradSq sq;
+  if (fused) {
+    WgradTail tail;
+    try {
+      tail = wgrad_tail_ranges(targets, skipped, arena->numel());
+    } catch (const std::invalid_argument& e) {
+      TORCH_CHECK(false, e.what());
+    }
+    sq.base = arena->data_ptr<float>();
+    sq.tail = tail.tail;
+    for (const auto& [lo, hi] : tail.ranges) {
       sq.lo[sq.nr] = lo;
-      sq.hi[sq.nr] = hi;
-      ++sq.nr;
-      rest += hi - lo;
-    };
-    for (const auto& [lo, hi] : iv) {
-      gap(cur, lo);
-      cur = std::max(cur, hi);
+      sq.hi[sq.nr++] = hi;
     }
-    gap(cur, n);
-    sq.tail = (int)std::min<int64_t>(64, std::max<int64_t>(1, (rest + 256 * 16 - 1) / (256 * 16)));
   }
-  const size_t total = dys.size();
-  // launches of <= WGRAD_MULTI_MAX problems with balanced tile counts (each launch's
-  // K-split tail then fills its last round; 32 + 18 problems left a 0.9-round launch)
-  int kmax = 0;
-  for (const auto& t : dys) kmax = std::max<int>(kmax, (int)t.size(0));
-  const int T = wgrad_multi_tile(kmax);
-  std::vector<int64_t> ptiles(total);
-  int64_t all_tiles = 0;
-  for (size_t i = 0; i < total; ++i) {
-    ptiles[i] = ((dys[i].size(1) + T - 1) / T) * ((xs[i].size(1) + T - 1) / T);
-    all_tiles += ptiles[i];
+  TORCH_CHECK(!with_emb || fused || nl == 1, "wgrad_multi: embedding parts need sq fusion or one launch");
+  int64_t all_tiles = 0, ws_floats = 0;
+  bool split = false;
+  for (const WgradLaunch& l : plan.launches) {
+    all_tiles += l.tiles;
+    ws_floats += l.ws_floats;
+    split = split || l.split > 1;
   }
-  const size_t L = (total + WGRAD_MULTI_MAX - 1) / WGRAD_MULTI_MAX;
-  std::vector<size_t> cuts{0};
-  int64_t cum = 0;
-  for (size_t i = 0; i + 1 < total && cuts.size() < L; ++i) {
-    cum += ptiles[i];
-    const bool full = i + 1 - cuts.back() == (size_t)WGRAD_MULTI_MAX;
-    if (full || cum * (int64_t)L >= all_tiles * (int64_t)cuts.size()) cuts.push_back(i + 1);
-  }
-  cuts.push_back(total);
-  bool ok = true;
-  for (size_t c = 0; c + 1 < cuts.size(); ++c) ok = ok && cuts[c + 1] - cuts[c] <= (size_t)WGRAD_MULTI_MAX;
-  if (!ok) {  // cannot balance within the problem limit: plain chunks
-    cuts.clear();
-    for (size_t a = 0; a < total; a += WGRAD_MULTI_MAX) cuts.push_back(a);
-    cuts.push_back(total);
-  }
-  int used = 0;  // partial slots written by earlier launches
-  for (size_t ci = 0; ci + 1 < cuts.size(); ++ci) {
-    const size_t a = cuts[ci], e = cuts[ci + 1];
-    // K-split tail of wide launches: workspace from the caching allocator (the capture's
-    // pool inside a graph), tickets in a per-device buffer every last piece resets
-    float* sws = nullptr;
-    int* scnt = nullptr;
-    Tensor ws_t;
-    {
-      int64_t ct = 0;
-      for (size_t i = a; i < e; ++i) ct += ptiles[i];
-      const int64_t nf = wgrad_split_ws_floats((int)ct, T);
-      if (nf > 0) {
-        ws_t = at::empty({nf}, dys[0].options().dtype(F32));
-        sws = ws_t.data_ptr<float>();
-        scnt = split_tickets(dys[0].device());
-      }
+  const int n_emb = with_emb ? wgrad_embed_workgroups(we, plan.T == 128) : 0;
+  TORCH_CHECK(!fused || all_tiles + sq.tail + n_emb <= np, "wgrad_multi: grad-norm partials too small: ", np,
+              " slots for ", all_tiles, " tiles + ", sq.tail, " tail + ", n_emb, " embedding workgroups");
+  // K-split tails: the workspace of every launch from the caching allocator (the capture's
+  // pool inside a graph); tickets from the caller, or zero-filled here outside a capture
+  Tensor ws_t, tickets_t;
+  if (split) {
+    if (have_tickets) {
+      tickets_t = *split_tickets;
+    } else {
+      hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+      TORCH_CHECK(hipStreamIsCapturing(cur_stream(), &cap) == hipSuccess && cap == hipStreamCaptureStatusNone,
+                  "wgrad_multi: a captured launch with K-split tail tiles needs tickets that outlive the graph: "
+                  "pass tickets=ops.wgrad_tickets(device), allocated before the capture");
+      tickets_t = at::zeros({WGRAD_TICKETS}, dys[0].options().dtype(at::kInt));
     }
-    std::vector<Tensor> d(dys.begin() + a, dys.begin() + e), x(xs.begin() + a, xs.begin() + e),
-        w(dws.begin() + a, dws.begin() + e);
-    std::vector<c10::optional<Tensor>> b(dbs.begin() + a, dbs.begin() + e);
-    std::vector<GemmArgs> probs = wgrad_probs(d, x, w, b, nullptr, nullptr);
-    if (!fused) {
-      gemm_wgrad_multi(probs.data(), (int)probs.size(), cur_stream(), store, nullptr,
-                       (with_emb && e == total) ? &we : nullptr, sws, scnt);
-      continue;
-    }
+    ws_t = at::empty({ws_floats}, dys[0].options().dtype(F32));
+  }
+
+  // ---- launch
+  int64_t used = 0, ws_off = 0;  // partial slots / workspace floats of earlier launches
+  for (size_t i = 0; i < nl; ++i) {
+    const WgradLaunch& l = plan.launches[i];
+    const bool last = i + 1 == nl;  // tail ranges, zero fill and embedding workgroups ride in the last launch
     WgradSq s = sq;
-    s.parts = sq_parts->data_ptr<float>() + used;
-    s.nparts = np - used;
-    if (e < total) {  // tail ranges, zero fill and embedding workgroups ride in the last launch
-      s.nr = 0;
-      s.tail = 0;
+    if (fused) {
+      s.parts = sq_parts->data_ptr<float>() + used;
+      s.nparts = np - (int)used;
+      if (!last) s.nr = s.tail = 0;
     }
-    used += gemm_wgrad_multi(probs.data(), (int)probs.size(), cur_stream(), store, &s,
-                             (with_emb && e == total) ? &we : nullptr, sws, scnt);
+    gemm_wgrad_multi(probs.data(), l, plan.T, cur_stream(), store, fused ? &s : nullptr,
+                     with_emb && last ? &we : nullptr, l.split > 1 ? ws_t.data_ptr<float>() + ws_off : nullptr,
+                     l.split > 1 ? tickets_t.data_ptr<int>() : nullptr);
+    used += l.tiles;
+    ws_off += l.ws_floats;
   }
-  TORCH_CHECK(!with_emb || fused || total <= (size_t)WGRAD_MULTI_MAX, "wgrad_multi: embedding parts need sq fusion "
-              "or one launch");
 }
 
-// grad-norm partial slots the embedding workgroups of a wgrad_multi launch take
-int64_t wgrad_embed_slots(int64_t B, int64_t N, int64_t D, int64_t owners, int64_t n_ln, int64_t ln_C, bool wide) {
+// (T, CUs, then (first, count, tiles, split, whole, pieces, ws_floats) per launch) of the
+// launches linear_wgrad_multi would make for these problems (host only: no launch)
+std::vector<int64_t> wgrad_multi_plan_op(std::vector<int64_t> nouts, std::vector<int64_t> ks,
+                                         std::vector<int64_t> tokens) {
+  TORCH_CHECK(nouts.size() == ks.size() && nouts.size() == tokens.size(), "wgrad_multi_plan: one Nout, K, tokens each");
+  std::vector<WgradShape> shapes;
+  for (size_t i = 0; i < nouts.size(); ++i) shapes.push_back({nouts[i], ks[i], tokens[i]});
+  const WgradPlan plan = wgrad_plan_of(shapes);
+  std::vector<int64_t> out{plan.T, gemm_cu_count()};
+  for (const WgradLaunch& l : plan.launches)
+    out.insert(out.end(), {l.first, l.count, l.tiles, l.split, l.whole, l.pieces, l.ws_floats});
+  return out;
+}
+
+// grad-norm partial slots the embedding workgroups of a wgrad_multi launch over `tokens`
+// rows take
+int64_t wgrad_embed_slots(int64_t B, int64_t N, int64_t D, int64_t owners, int64_t n_ln, int64_t ln_C, int64_t tokens) {
   WgradEmbed we{};
   we.e.B = (int)B; we.e.N = (int)N; we.e.D = (int)D; we.e.owners = (int)owners;
   float dummy = 0.f;
   if (n_ln > 0) { we.rf.ws = &dummy; we.rf.G = (int)n_ln; we.rf.C = (int)ln_C; }
-  return wgrad_embed_workgroups(we, wide);
+  return wgrad_embed_workgroups(we, wgrad_multi_tile(tokens) == 128);
 }
 
 // fp32 <-> bf16 gradient wire (csrc/comm_wire.hip): one fused 16-B-vector
@@ -1316,8 +1290,10 @@ TORCH_LIBRARY(ddim_cold, m) {
         "Tensor(c!)? sq_parts=None, Tensor? arena=None, int lz_lo=0, int lz_hi=0, Tensor? emb_g=None, "
         "Tensor? emb_t=None, Tensor? emb_rng=None, int emb_site=0, float emb_p=0.0, Tensor(d!)? emb_cls=None, "
         "Tensor(e!)? emb_pos=None, Tensor(f!)? emb_temb=None, int emb_owners=0, Tensor? ln_ws=None, "
-        "Tensor? ln_ptrs=None, int[] ln_offs=[], int ln_C=0, int ln_R=0, bool ln_store=False) -> ()");
-  m.def("wgrad_embed_slots(int B, int N, int D, int owners, int n_ln, int ln_C, bool wide) -> int", &wgrad_embed_slots);
+        "Tensor? ln_ptrs=None, int[] ln_offs=[], int ln_C=0, int ln_R=0, bool ln_store=False, "
+        "Tensor(g!)? split_tickets=None) -> ()");
+  m.def("wgrad_multi_plan(int[] nouts, int[] ks, int[] tokens) -> int[]", &wgrad_multi_plan_op);
+  m.def("wgrad_embed_slots(int B, int N, int D, int owners, int n_ln, int ln_C, int tokens) -> int", &wgrad_embed_slots);
   m.def("layernorm_bwd(Tensor dy, Tensor x, Tensor mean, Tensor rstd, Tensor gamma, Tensor? g_res, "
         "Tensor(a!) dgamma, Tensor(b!) dbeta, int N, Tensor rng, int site_drop, float p_drop, int site_dp, "
         "float p_dp, bool emit_gy, Tensor(c!)? ws=None, Tensor? beta=None, Tensor(d!)? y_out=None, "

@@ -653,8 +653,7 @@ DC_INST_DMA(64, true, true, EPI_ATOMIC)
 // must stay under 4 KiB); one token split, so the epilogue is a plain
 // read-add-write (EPI_ACC: deterministic, no fp32 atomics).
 constexpr int WM_MAX = WGRAD_MULTI_MAX;
-constexpr int BIG_WG_K = 16384;  // tokens: 128 x 128 weight-gradient tiles from here
-// their LDS ring: 4 x 32 KiB, one workgroup per CU.  A 2-stage ring (two workgroups per CU,
+// the LDS ring of the 128 x 128 tiles (>= BIG_WG_K tokens, wgrad_plan.h): 4 x 32 KiB, one workgroup per CU.  A 2-stage ring (two workgroups per CU,
 // to soften the last-wave tail of ~5.1 tile rounds) took the vit_small_200 weight
 // gradients 638 -> 1,183 us (and 48 problems per launch did not merge its two launches)
 constexpr int BIG_WG_STAGES = 4;
@@ -1013,10 +1012,7 @@ int wgrad_embed_workgroups(const WgradEmbed& emb, bool wide) {
          (emb.rf.ws ? emb.rf.G * ((emb.rf.C + 15) / 16) : 0);
 }
 
-// K pieces for the tail tiles of a wide (one workgroup per CU) launch: with W whole rounds
-// of 256 tiles and R tiles left, R x s pieces take ceil(R s / 256) / s tile times instead
-// of one (profiles/wgrad_split_r6.txt); s = 1 (no split) when nothing is gained
-static int cu_count() {  // one wide workgroup per CU (256 on the MI355X)
+int gemm_cu_count() {  // one wide workgroup per CU (256 on the MI355X)
   static const int n = [] {
     int dev = 0, v = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
@@ -1026,30 +1022,10 @@ static int cu_count() {  // one wide workgroup per CU (256 on the MI355X)
   }();
   return n;
 }
-// workgroup slots of one round: one 128 x 128 (128 KiB ring) or three 64 x 64 (48 KiB)
-// weight-gradient workgroups per CU
-static int wgrad_slots(int T) { return (T == 128 ? 1 : 3) * cu_count(); }
-int wgrad_split_factor(int tiles, int T) {
-  const int C = wgrad_slots(T), R = tiles % C;
-  // 64 x 64 tiles (three workgroups per CU): splitting ViT-tiny's 12-tile tail in 6 pieces
-  // measured slower (0.7107 -> 0.7146 ms/step, profiles/wgrad_split_r6.txt) -- wide tiles only
-  if (R == 0 || T != 128) return 1;
-  int best = 1;
-  double bt = 1.0;
-  for (int s = 2; s <= WGRAD_MAX_SPLIT; ++s) {
-    const double t = (double)((R * s + C - 1) / C) / s;
-    if (t < bt - 1e-9) { bt = t; best = s; }
-  }
-  return best;
-}
-int wgrad_multi_tile(int kmax) { return kmax >= BIG_WG_K ? 128 : 64; }
-int64_t wgrad_split_ws_floats(int tiles, int T) {
-  const int s = wgrad_split_factor(tiles, T);
-  return s > 1 ? (int64_t)(tiles % wgrad_slots(T)) * s * (T * T + T) : 0;
-}
 
-int gemm_wgrad_multi(const GemmArgs* probs, int n, hipStream_t stream, bool store, const WgradSq* sq,
-                     const WgradEmbed* emb, float* split_ws, int* split_cnt) {
+void gemm_wgrad_multi(const GemmArgs* probs, const WgradLaunch& l, int T, hipStream_t stream, bool store,
+                      const WgradSq* sq, const WgradEmbed* emb, float* split_ws, int* split_cnt) {
+  const int n = l.count;
   if (n < 1 || n > WM_MAX) throw std::runtime_error("gemm_wgrad_multi: 1..WGRAD_MULTI_MAX problems per launch");
   WgradMulti gm{};
   gm.n = n;
@@ -1061,20 +1037,23 @@ int gemm_wgrad_multi(const GemmArgs* probs, int n, hipStream_t stream, bool stor
   // rounds: 0.838 vs 0.824 ms/step), 128 x 64 tiles (24 % fewer operand bytes, same
   // 60-61 us launch), a 4-stage ring (0.833).  Long reductions (>= BIG_WG_K tokens,
   // vit_small_200) take 128 x 128 tiles of 8 waves with a 4-stage 128 KiB ring.
-  int kmax = 0;
-  for (int i = 0; i < n; ++i) kmax = std::max(kmax, probs[i].K);
-  const int T = kmax >= BIG_WG_K ? 128 : 64;
+  if (T != 64 && T != 128) throw std::logic_error("gemm_wgrad_multi: tile edge");
   for (int i = 0; i < n; ++i) {
-    const GemmArgs& a = probs[i];
+    const GemmArgs& a = probs[l.first + i];
     if (a.N % 4 != 0) throw std::runtime_error("gemm_wgrad_multi: output width must be a multiple of 4");
+    if (T == 64 && a.K >= BIG_WG_K) throw std::logic_error("gemm_wgrad_multi: tile edge below the plan's rule");
     WgDesc& d = gm.d[i];
     d.A = reinterpret_cast<const bf16*>(a.A); d.B = reinterpret_cast<const bf16*>(a.B);
     d.C = reinterpret_cast<float*>(a.C); d.bias = const_cast<float*>(a.bias);
     d.M = a.M; d.N = a.N; d.K = a.K; d.lda = a.lda; d.ldb = a.ldb; d.ldc = a.ldc;
     gm.tile_start[i] = tiles;
-    tiles += ((a.M + T - 1) / T) * ((a.N + T - 1) / T);
+    tiles += (int)wgrad_tiles(a.M, a.N, T);
   }
   for (int i = n; i <= WM_MAX; ++i) gm.tile_start[i] = tiles;
+  const int R = tiles - l.whole;
+  if (tiles != l.tiles || l.split < 1 || l.split > WGRAD_MAX_SPLIT || R < 0 || R > WGRAD_TICKETS ||
+      l.pieces != R * (l.split - 1) || (l.split == 1 && R != 0))
+    throw std::logic_error("gemm_wgrad_multi: the launch record does not match its problems");
   int extra = 0;
   if (emb != nullptr) {
     const int NT = T == 128 ? 512 : 256;
@@ -1091,34 +1070,26 @@ int gemm_wgrad_multi(const GemmArgs* probs, int n, hipStream_t stream, bool stor
   }
   if (sq != nullptr && sq->parts != nullptr) {
     if (sq->tail < 0 || sq->nr < 0 || sq->nr > WSQ_MAX_RANGES || sq->nparts < tiles + sq->tail + extra)
-      throw std::runtime_error("gemm_wgrad_multi: grad-norm partial buffer too small (nparts < tiles + tail + "
-                               "embedding workgroups) or more than 16 ranges");
+      throw std::logic_error("gemm_wgrad_multi: grad-norm partial buffer too small (nparts < tiles + tail + "
+                             "embedding workgroups) or more than 16 ranges");
     gm.sq = *sq;
     extra += sq->tail;
   }
   static_assert(sizeof(WgradMulti) <= 4000, "kernel argument block");
-  gm.whole = tiles;
-  gm.split = 1;
-  int pieces = 0;
-  if (split_ws != nullptr && split_cnt != nullptr) {
-    const int s = wgrad_split_factor(tiles, T);
-    if (s > 1) {
-      const int R = tiles % wgrad_slots(T);
-      gm.whole = tiles - R;
-      gm.split = s;
-      gm.ws = split_ws;
-      gm.cnt = split_cnt;
-      pieces = R * s - R;  // extra workgroups beyond one per tile
-    }
+  gm.whole = l.whole;
+  gm.split = l.split;
+  if (l.split > 1) {
+    if (split_ws == nullptr || split_cnt == nullptr) throw std::logic_error("gemm_wgrad_multi: split without workspace");
+    gm.ws = split_ws;
+    gm.cnt = split_cnt;
   }
   if (T == 128) {
     constexpr int lds = BIG_WG_STAGES * 2 * 128 * 128;  // stages x (A + B) 128-wide, 64-deep images
-    hipLaunchKernelGGL((gemm_wgrad_multi_kernel<128, BIG_WG_STAGES, 128, 4, 2>), dim3(tiles + pieces + extra), dim3(512),
+    hipLaunchKernelGGL((gemm_wgrad_multi_kernel<128, BIG_WG_STAGES, 128, 4, 2>), dim3(tiles + l.pieces + extra), dim3(512),
                        lds, stream, gm);
   } else {
-    hipLaunchKernelGGL((gemm_wgrad_multi_kernel<64, 3>), dim3(tiles + pieces + extra), dim3(256),
+    hipLaunchKernelGGL((gemm_wgrad_multi_kernel<64, 3>), dim3(tiles + l.pieces + extra), dim3(256),
                        3 * (64 * 128 + 64 * 128), stream, gm);
   }
-  return tiles;
 }
 

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdexcept>
+#include "wgrad_plan.h"
 
 enum GemmEpi : int {
   EPI_BF16 = 0,    // C bf16 = acc (+bias)
@@ -95,16 +96,14 @@ int gemm_set_tile_override(int cfg);
 uint32_t* gemm_set_stamps(uint32_t* buf);
 void gemm_dgrad(const GemmArgs& a, int epi, hipStream_t stream);
 void gemm_wgrad(const GemmArgs& a, int splits, hipStream_t stream);
-// every weight gradient of a step (n <= 32 problems) in one launch, unsplit (plain read-add-write)
-// store: every target is zero on entry (plain stores instead of read-add-write)
+// every weight gradient of a step in one launch per <= WGRAD_MULTI_MAX problems (plain
+// read-add-write); store: every target is zero on entry (plain stores instead)
 // Grad-norm partials fused into the weight-gradient launch (single process: it is the
 // last writer of the gradient arena): every output tile writes the sum of squares of
 // its final dW (+ db) values to parts[tile]; `tail` extra workgroups sum the squares
 // of the arena ranges [lo, hi) no weight-gradient tile writes (embeddings, LayerNorms:
 // final before this launch) into parts[tiles + j], and zero parts[tiles + tail ..
 // nparts).  The optimizer then reads the same partial layout sqnorm writes.
-constexpr int WSQ_MAX_RANGES = 16;
-constexpr int WGRAD_MULTI_MAX = 32;  // problems per gemm_wgrad_multi launch (kernel-argument block)
 struct WgradSq {
   float* parts = nullptr;
   int nparts = 0;
@@ -112,23 +111,18 @@ struct WgradSq {
   int nr = 0, tail = 0;
   int64_t lo[WSQ_MAX_RANGES], hi[WSQ_MAX_RANGES];
 };
-// returns the output tiles launched (grad-norm partial slots used before the tail);
-// sq->tail = 0: no tail workgroups, no zero fill (all but the last launch of a step).
-// emb (optional): the embedding gradients and the LayerNorm slot finalize ride in the
+// One launch of the plan (wgrad_plan.h): problems probs[l.first .. l.first + l.count) on
+// T x T tiles.  sq->tail = 0: no tail workgroups, no zero fill (all but the last launch of a
+// step).  emb (optional): the embedding gradients and the LayerNorm slot finalize ride in the
 // launch as extra workgroups (embed_parts.h), each writing the grad-norm partial of its
 // outputs after the tail's slots.
 struct WgradEmbed;  // below
-// split_ws / split_cnt: workspace of wgrad_split_ws_floats(tiles, T) floats and zeroed
-// tickets -- the tail tiles past the last whole round of workgroup slots (256 CUs x 1
-// wide or x 3 64 x 64 workgroups) run as wgrad_split_factor(tiles, T) K pieces each,
-// summed in piece order (deterministic)
-constexpr int WGRAD_MAX_SPLIT = 6;
-int wgrad_split_factor(int tiles, int T);
-int wgrad_multi_tile(int kmax);  // output tile edge gemm_wgrad_multi uses for reductions over kmax tokens
-int64_t wgrad_split_ws_floats(int tiles, int T);
-int gemm_wgrad_multi(const GemmArgs* probs, int n, hipStream_t stream, bool store = false,
-                     const WgradSq* sq = nullptr, const WgradEmbed* emb = nullptr, float* split_ws = nullptr,
-                     int* split_cnt = nullptr);
+// split_ws / split_cnt (l.split > 1): workspace of l.ws_floats floats and zeroed tickets --
+// the tail tiles past the last whole round of workgroup slots run as l.split K pieces each,
+// summed in piece order (deterministic); each tile's last piece resets its ticket
+void gemm_wgrad_multi(const GemmArgs* probs, const WgradLaunch& l, int T, hipStream_t stream, bool store,
+                      const WgradSq* sq, const WgradEmbed* emb, float* split_ws, int* split_cnt);
+int gemm_cu_count();  // compute units of the current device: the `cus` of wgrad_plan
 int wgrad_embed_workgroups(const WgradEmbed& emb, bool wide);  // extra workgroups (= grad-norm slots) emb takes
 
 // LayerNorm (layernorm.hip)

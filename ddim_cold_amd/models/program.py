@@ -436,7 +436,7 @@ class ViTProgram:
                       training: bool = True, wgrad: Optional[Callable] = None,
                       ln_ws: Optional[torch.Tensor] = None, embed_with_block0: bool = False, ln_final=None,
                       wgrad_flush=None, wgrad_store: bool = False, wgrad_sq=None,
-                      embed_fused=None) -> Iterator[int]:
+                      embed_fused=None, wgrad_tickets=None) -> Iterator[int]:
         """Hand-written backward; yields the block index after each block's input
         gradients are issued (L-1 first, then ..., 0) and -1 after the embedding grads.
 
@@ -465,6 +465,8 @@ class ViTProgram:
         cls / pos / time-embedding gradients and the LayerNorm finalize (``ln_final``,
         ``ln_offs`` = its destinations' arena offsets) run as extra workgroups of the
         weight-gradient launch (``owners`` >= the distinct timesteps of a batch).
+        ``wgrad_tickets``: the caller's :func:`ops.wgrad_tickets` buffer for the deferred
+        launches (a captured backward over >= 16,384 tokens needs one).
         Measured slower on MI355X and removed: weight gradients riding in the
         input-gradient launches, one grouped launch per block, a side-stream branch
         for them, the proj input gradient inside the attention backward, the
@@ -560,7 +562,8 @@ class ViTProgram:
             elif i == 0 and embed_with_block0:
                 gpatch = self._embed_backward(P, G, S, g, rng, pd, wgrad, ln_final)
             if bucketed and (i in wgrad_flush or (i == 0 and embed_with_block0)) and jobs:
-                ops.linear_wgrad_multi(jobs, store=wgrad_store)  # this bucket's weight gradients: final now
+                # this bucket's weight gradients: final now
+                ops.linear_wgrad_multi(jobs, store=wgrad_store, tickets=wgrad_tickets)
                 keep.append(jobs)
                 jobs = []
             yield i
@@ -575,7 +578,8 @@ class ViTProgram:
                 for job in jobs:
                     ops.linear_wgrad(*job)
             else:
-                ops.linear_wgrad_multi(jobs, store=wgrad_store and not bucketed, sq=wgrad_sq, embed=emb_spec)
+                ops.linear_wgrad_multi(jobs, store=wgrad_store and not bucketed, sq=wgrad_sq, embed=emb_spec,
+                                       tickets=wgrad_tickets)
             keep.append(jobs)
         keep.append((gpatch, lf))
         self._keep = keep  # operands of the queued launches stay referenced until the next step

@@ -345,15 +345,30 @@ def wire_unpack(src, dst):
     dst.copy_(src)
 
 
-def wgrad_embed_slots(B: int, N: int, D: int, owners: int, n_ln: int, ln_C: int, wide: bool) -> int:
+WGRAD_WIDE_TOKENS = 16384  # csrc/wgrad_plan.h BIG_WG_K
+WGRAD_TICKETS = 4096       # csrc/wgrad_plan.h
+
+
+def wgrad_embed_slots(B: int, N: int, D: int, owners: int, n_ln: int, ln_C: int, tokens: int) -> int:
     """Grad-norm partial slots (= extra workgroups) the embedding parts of
-    :func:`linear_wgrad_multi` take (``wide``: the 512-thread tiles of >= 16,384-token
-    reductions)."""
-    nt = 512 if wide else 256
+    :func:`linear_wgrad_multi` take in a launch whose longest reduction runs over
+    ``tokens`` rows (512-thread workgroups from ``WGRAD_WIDE_TOKENS``, 256-thread ones
+    below).  The loaded extension's own count when there is one, like :func:`ln_ws_rows`."""
+    if native_available():
+        return int(_ops().wgrad_embed_slots(B, N, D, owners, n_ln, ln_C, tokens))
+    nt = 512 if tokens >= WGRAD_WIDE_TOKENS else 256
     return -(-(N * D) // nt) + owners * -(-D // 16) + (n_ln * -(-ln_C // 16) if n_ln else 0)
 
 
-def linear_wgrad_multi(jobs, store: bool = False, sq=None, embed=None):
+def wgrad_tickets(device) -> torch.Tensor:
+    """A zeroed ticket buffer for the K-split tail tiles of :func:`linear_wgrad_multi`
+    (``tickets=``).  Its owner allocates it outside any graph capture and keeps it as long
+    as a graph that uses it; every launch leaves it zero, so launches ordered on one stream
+    share one buffer."""
+    return torch.zeros(WGRAD_TICKETS, dtype=torch.int32, device=device)
+
+
+def linear_wgrad_multi(jobs, store: bool = False, sq=None, embed=None, tickets=None):
     """Every ``(dy, x, dw, db)`` weight-gradient job of a step (<= 32) in ONE launch
     (csrc/gemm.hip ``gemm_wgrad_multi_kernel``; unsplit, deterministic).  ``store``:
     the targets are zero (``dW = dy^T x`` written, not added: no read of dW).
@@ -370,7 +385,12 @@ def linear_wgrad_multi(jobs, store: bool = False, sq=None, embed=None):
     and, with ``ln = (ws, dst_ptrs, offs, C, R, store)``, the LayerNorm slot finalize
     ride in the same launch as extra workgroups (each writing the grad-norm partials of
     its outputs); the patch-row gradient comes from the last LayerNorm backward
-    (:func:`layernorm_bwd` ``gp_out``).  Deterministic."""
+    (:func:`layernorm_bwd` ``gp_out``).  Deterministic.
+
+    ``tickets`` (:func:`wgrad_tickets`): reductions over >= 16,384 tokens run the tiles
+    past the last whole round of workgroups as K pieces that take a ticket each.  Without
+    it an eager call zero-fills a buffer of its own; a call inside a graph capture that
+    needs tickets raises.  ``torch.ops.ddim_cold.wgrad_multi_plan`` reports the launches."""
     if not jobs:
         return
     if _hip(jobs[0][0]):  # (more than 32 jobs: consecutive launches of <= 32)
@@ -378,13 +398,14 @@ def linear_wgrad_multi(jobs, store: bool = False, sq=None, embed=None):
         parts, arena, (lo, hi) = (None, None, (0, 0)) if sq is None else \
             (sq[0], sq[1], sq[2] if sq[2] is not None else (0, 0))
         if embed is None:
-            _ops().linear_wgrad_multi(dys, xs, dws, dbs, bool(store), parts, arena, int(lo), int(hi))
+            _ops().linear_wgrad_multi(dys, xs, dws, dbs, bool(store), parts, arena, int(lo), int(hi),
+                                      split_tickets=tickets)
             return
         g, t, rng, site, p, dcls, dpos, dtemb, owners, ln = embed
         lw, lp, loffs, lC, lR, lst = ln if ln is not None else (None, None, [], 0, 0, False)
         _ops().linear_wgrad_multi(dys, xs, dws, dbs, bool(store), parts, arena, int(lo), int(hi), g, t, rng,
                                   int(site), float(p), dcls, dpos, dtemb, int(owners), lw, lp,
-                                  [int(o) for o in loffs], int(lC), int(lR), bool(lst))
+                                  [int(o) for o in loffs], int(lC), int(lR), bool(lst), tickets)
         return
     for dy, x, dw, db in jobs:
         if store:

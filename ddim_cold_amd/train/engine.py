@@ -246,6 +246,9 @@ class TrainEngine:
         tiles = sum(-(-p.shape[0] // 64) * -(-(p[0].numel()) // 64) for p in model.parameters() if p.dim() >= 2)
         self._sq_tiles = tiles
         self.sqnorm = torch.zeros(ops.sq_parts_size(tiles), dtype=torch.float32, device=dev)
+        # tickets of the weight-gradient launches' K-split tails: this engine's own, allocated
+        # here (never inside a capture) and shared by its graphs, whose launches one stream orders
+        self.wgrad_tickets = ops.wgrad_tickets(dev) if self.is_cuda else None
         self.loss_last = torch.zeros(1, dtype=torch.float32, device=dev)
         self.loss_ema = torch.full((1,), cfg.ema_init, dtype=torch.float32, device=dev)
         # the comm stream is created once and kept across set_comm_layout() (a stream
@@ -569,7 +572,7 @@ class TrainEngine:
         D, M = c.dim, B * c.tokens
         rows = ops.ln_ws_rows(M)
         nparts = ops.sq_parts_size(self._sq_tiles + ops.wgrad_embed_slots(
-            B, c.tokens, D, self._emb_owners(B), len(self.ln_order), 2 * D, M >= 16384))
+            B, c.tokens, D, self._emb_owners(B), len(self.ln_order), 2 * D, M))
         if (self.ln_ws is not None and self.ln_ws.shape[1] == rows and self.sqnorm.numel() >= nparts):
             return
         if self.is_cuda and torch.cuda.is_current_stream_capturing():
@@ -742,7 +745,7 @@ class TrainEngine:
                                              ln_ws=self.ln_ws, embed_with_block0=merge, ln_final=ln_final,
                                              wgrad_flush=flush_at, wgrad_store=overwrite,
                                              wgrad_sq=(self.sqnorm, self.opt_g, self.lazy) if fuse_sq else None,
-                                             embed_fused=emb_fused):
+                                             embed_fused=emb_fused, wgrad_tickets=self.wgrad_tickets):
                 if i in self.bucket_after and (self.segmented or i == -1):
                     hi = self.ln_done_at[i]
                     if ln_final is not None:

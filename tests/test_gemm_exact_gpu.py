@@ -13,7 +13,9 @@ BF16 / QKV / GELU epilogues and runs as 256x128 elsewhere (128x128 for DGELU); c
 128x64 for transposed B; DGELU's 256-row config is the 128-row one.  Ring depth: 256x192
 always 2, 256x128 always 3, the others 3 when the grid exceeds 256 x per_cu4 workgroups
 with at most 8 k-tiles per slice, else 4.  ``linear_wgrad_multi`` has its own kernel and
-no plan: its 64 / 128 tile follows the token count (>= 16,384: 128x128).
+its own plan (csrc/wgrad_plan.h, ``torch.ops.ddim_cold.wgrad_multi_plan``): a 64x64 tile,
+or 128x128 from ``ops.WGRAD_WIDE_TOKENS`` tokens, launches of at most 32 problems, and on
+the wide tile the tiles past the last whole round of CUs in up to 6 K pieces each.
 
 A new tile configuration joins TILES in ops/gemm_check.py and with it the grids of
 sections (a) and (b) here.
@@ -290,9 +292,35 @@ def test_wgrad_exact(T):
             gc.run_wgrad(T, Nout, K, DEV, db)
 
 
+def wgrad_multi_plan(shapes, T):
+    """(tile edge, [(first, count, tiles, split, whole, pieces, ws_floats) per launch]) of
+    ``linear_wgrad_multi`` over ``shapes`` = (Nout, K, ...) at ``T`` tokens."""
+    v = [int(i) for i in torch.ops.ddim_cold.wgrad_multi_plan([s[0] for s in shapes], [s[1] for s in shapes],
+                                                              [T] * len(shapes))]
+    return v[0], [tuple(v[i:i + 7]) for i in range(2, len(v), 7)]
+
+
+def assert_wgrad_plan(shapes, T, tile, launches=1, split=1, whole=None):
+    """The launches are the ones the case names: ``tile`` x ``tile`` output tiles, ``launches``
+    launches covering the problems in order, every launch in ``split`` K pieces past its
+    first ``whole`` tiles (None: not named)."""
+    edge, recs = wgrad_multi_plan(shapes, T)
+    assert edge == tile and len(recs) == launches, f"plan {edge, recs}: not {launches} launch(es) of {tile}-tiles"
+    nxt = 0
+    for first, count, tiles, s, wh, pieces, ws in recs:
+        assert first == nxt and 1 <= count <= 32
+        nxt += count
+        assert tiles == sum(-(-n // tile) * -(-k // tile) for n, k, *_ in shapes[first:first + count])
+        assert s == split and (whole is None or wh == whole), f"plan {recs}: not split {split} after {whole} tiles"
+        assert pieces == (tiles - wh) * (s - 1) and ws == ((tiles - wh) * s * (tile * tile + tile) if s > 1 else 0)
+    assert nxt == len(shapes)
+    return recs
+
+
 @pytest.mark.parametrize("store", [False, True])
 @pytest.mark.parametrize("T", gc.WGRAD_TOKENS)
 def test_wgrad_multi_exact(T, store):
+    assert_wgrad_plan(gc.wgrad_shapes(), T, 64)
     gc.run_wgrad_multi(T, gc.wgrad_shapes(), DEV, store)
 
 
@@ -300,10 +328,133 @@ def test_wgrad_multi_exact(T, store):
 def test_wgrad_multi_wide_split_tail(store):
     """>= 16,384 tokens: 128x128 tiles; 10 tiles, all in the K-split tail (6 pieces each):
     exact and bit-identical over three launches."""
+    assert assert_wgrad_plan(gc.WGRAD_BIG_SHAPES, gc.WGRAD_BIG_TOKENS, 128, split=6, whole=0)[0][2] == 10
     gc.run_wgrad_multi(gc.WGRAD_BIG_TOKENS, gc.WGRAD_BIG_SHAPES, DEV, store, lo=-2, hi=2, repeats=3)
 
 
 @pytest.mark.parametrize("T,store", [(200, False), (200, True), (gc.WGRAD_BIG_TOKENS, False), (gc.WGRAD_BIG_TOKENS, True)])
 def test_wgrad_multi_sq_partials(T, store):
-    shapes = gc.wgrad_shapes() if T < 16384 else gc.WGRAD_BIG_SHAPES
+    assert gc.WGRAD_BIG_TOKENS >= ops.WGRAD_WIDE_TOKENS > 200
+    if T < ops.WGRAD_WIDE_TOKENS:
+        shapes = gc.wgrad_shapes()
+        assert_wgrad_plan(shapes, T, 64)
+    else:
+        shapes = gc.WGRAD_BIG_SHAPES
+        assert_wgrad_plan(shapes, T, 128, split=6, whole=0)
     gc.run_wgrad_sq(T, shapes, DEV, store)
+
+
+def _big_split_jobs():
+    """``WGRAD_BIG_SHAPES`` at 16,392 tokens with zeroed targets (``store=True``): 10 wide
+    tiles, all in the split tail, 6 pieces each; fp64 truths and canaries."""
+    T, shapes = gc.WGRAD_BIG_TOKENS, gc.WGRAD_BIG_SHAPES
+    assert assert_wgrad_plan(shapes, T, 128, split=6, whole=0)[0][2] == 10
+    g = gc._gen(10)
+    return (list(z) for z in zip(*[gc._wgrad_job(T, n, k, hb, True, g, DEV, -2, 2) for n, k, hb in shapes]))
+
+
+def _scrub(jobs):
+    for _, _, dw, db in jobs:  # store=True never reads the targets: a NaN left over shows a tile not written
+        dw.fill_(float("nan"))
+        if db is not None:
+            db.fill_(float("nan"))
+
+
+def _bits(jobs):
+    return [gc._bits(t).clone() for _, _, dw, db in jobs for t in (dw, db) if t is not None]
+
+
+def test_wgrad_multi_tickets_across_graphs():
+    """One caller-owned ticket buffer serves two graphs captured in two pools, replayed in
+    either order: whichever runs first finds the tickets zero and leaves them zero."""
+    jobs, truths, oks = _big_split_jobs()
+    tickets = ops.wgrad_tickets(DEV)
+    assert tickets.dtype == torch.int32 and tickets.numel() == ops.WGRAD_TICKETS and not tickets.any()
+    graphs = []
+    for _ in range(2):
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, pool=torch.cuda.graph_pool_handle()):
+            ops.linear_wgrad_multi(jobs, store=True, tickets=tickets)
+        graphs.append(g)
+    a, b = graphs
+    seen = []
+    for name, g in (("B", b), ("A", a), ("B again", b)):
+        _scrub(jobs)
+        g.replay()
+        torch.cuda.synchronize()
+        gc._wgrad_check(jobs, truths, oks, f"linear_wgrad_multi graph {name}")
+        assert not tickets.any(), f"graph {name} left a ticket taken"
+        seen.append(_bits(jobs))
+    for s in seen[1:]:
+        assert all(torch.equal(x, y) for x, y in zip(s, seen[0])), "weight gradients differ between replays"
+
+
+def test_wgrad_multi_capture_needs_tickets():
+    """Inside a capture a launch with split tiles and no ``tickets`` is refused before it
+    allocates or launches; the eager call fills its own."""
+    jobs, truths, oks = _big_split_jobs()
+    _scrub(jobs)
+    before = _bits(jobs)
+    other = torch.zeros(64, device=DEV)
+    with pytest.raises(RuntimeError, match="wgrad_tickets"):
+        with torch.cuda.graph(torch.cuda.CUDAGraph()):
+            other.add_(1.0)  # the capture holds other work, as a step's does
+            ops.linear_wgrad_multi(jobs, store=True)
+    torch.cuda.synchronize()
+    assert all(torch.equal(x, y) for x, y in zip(_bits(jobs), before))
+    ops.linear_wgrad_multi(jobs, store=True)
+    gc._wgrad_check(jobs, truths, oks, "linear_wgrad_multi after a refused capture")
+
+
+def _int_jobs(shapes, T, g, arena=None):
+    """Integer jobs whose every product is non-zero somewhere; ``arena``: dw / db are views of it."""
+    jobs, off = [], 0
+    for n, k in shapes:
+        dy, x = gc.int_operands((T, n), 1, 3, g, device=DEV), gc.int_operands((T, k), 1, 3, g, device=DEV)
+        if arena is None:
+            dw, db = gc.int_operands((n, k), -8, 8, g, torch.float32, DEV), gc.int_operands((n,), -8, 8, g, torch.float32, DEV)
+        else:
+            dw, db = arena[off:off + n * k].view(n, k), arena[off + n * k:off + n * k + n]
+            off += n * k + n
+        jobs.append((dy, x, dw, db))
+    return jobs
+
+
+def test_wgrad_multi_checks_before_launching():
+    """A refused call has written nothing: embedding parts over two launches without ``sq``
+    (33 problems), and grad-norm partials too small for the tiles of two launches."""
+    g = gc._gen(12)
+    jobs = _int_jobs([(8, 8)] * 33, 8, g)
+    B, N, D = 2, 3, 8
+    emb = [gc.int_operands(s, 1, 3, g, torch.float32, DEV) for s in ((B, N, D), (D,), (N * D,), (4, D))]
+    t = torch.tensor([1, 2], device=DEV)
+    spec = (emb[0], t, gc._rng(DEV), 3, 0.0, emb[1], emb[2], emb[3], B, None)
+    assert_wgrad_plan([(8, 8)] * 33, 8, 64, launches=2)
+    before = _bits(jobs) + [gc._bits(e).clone() for e in emb]
+    with pytest.raises(RuntimeError, match="one launch"):
+        ops.linear_wgrad_multi(jobs, embed=spec)
+    torch.cuda.synchronize()
+    assert all(torch.equal(x, y) for x, y in zip(_bits(jobs) + [gc._bits(e) for e in emb], before))
+
+    shapes = [(320, 320)] * 44  # 1,100 64x64 tiles in two launches: more than 1,024 slots
+    arena = gc.int_operands((sum(n * k + n for n, k in shapes),), -8, 8, g, torch.float32, DEV)
+    jobs = _int_jobs(shapes, 8, g, arena)
+    recs = assert_wgrad_plan(shapes, 8, 64, launches=2)
+    parts = torch.full((1024,), 7.0, device=DEV)
+    assert recs[0][2] < parts.numel() < recs[0][2] + recs[1][2]  # the first launch alone would fit
+    before = [gc._bits(arena).clone(), gc._bits(parts).clone()]
+    with pytest.raises(RuntimeError, match="grad-norm partials"):
+        ops.linear_wgrad_multi(jobs, sq=(parts, arena, None))
+    with pytest.raises(RuntimeError, match="grad-norm partials"):  # under the buffer's minimum size
+        ops.linear_wgrad_multi(jobs, sq=(torch.zeros(256, device=DEV), arena, None))
+    torch.cuda.synchronize()
+    assert torch.equal(gc._bits(arena), before[0]) and torch.equal(gc._bits(parts), before[1])
+
+
+def test_engines_own_their_wgrad_tickets():
+    from ddim_cold_amd import build_model
+    from ddim_cold_amd.train.engine import EngineConfig, TrainEngine
+    engines = [TrainEngine(build_model("vit_tiny").cuda().train(), EngineConfig(use_graph=False)) for _ in range(2)]
+    a, b = (e.wgrad_tickets for e in engines)
+    assert a.data_ptr() != b.data_ptr() and a.numel() == b.numel() == ops.WGRAD_TICKETS
+    assert a.dtype == torch.int32 and not a.any() and not b.any()
