@@ -778,3 +778,214 @@ def run_wgrad_sq(T: int, shapes, device, store: bool, seed: int = 11, lo: int = 
     expect = int((arena.double() ** 2).sum().item())
     got = parts.double().sum().item()
     assert abs(got - expect) <= 1e-6 * expect, f"grad-norm partials sum {got!r}, exact {expect}"
+
+
+# ----------------------------------------------------------------------------- LayerNorm-fold consumers
+# The fold epilogue computes rstd * (acc - mean * c) + b with (mean, rstd) from the row
+# statistics st[m][K/32] = {sum x, sum x^2}.  ``st`` and ``c`` are inputs of the op, so the
+# probe *constructs* them instead of deriving them from ``a``: row m gets an integer mean code
+# mu_m and a standard deviation sigma_m in {1/2, 1, 2, 4}, i.e. totals sum x = K mu_m and
+# sum x^2 = K (sigma_m^2 + mu_m^2), split over the slots as distinct integers; column n gets an
+# integer code c_n; eps = 0.  For K a power of two 1/K is exact, so mean = mu_m, var = sigma_m^2,
+# rstd = 1 / sigma_m in {2, 1, 1/2, 1/4} and every later operation are exact in fp32 in any
+# order, with or without FMA contraction: the output is unique to the bit.  (This rests on the
+# hardware reciprocal square root being exact at 1/4, 1, 4 and 16; the returned ``ln_rstd`` is
+# asserted first -- see tests/test_gemm_exact_gpu.py for what was measured.)  For K = 192 / 384
+# the host's 1/K is rounded and the same probe is compared within a bound derived from the
+# operands (:func:`fold_bound`).
+FOLD_SIGMAS = (0.5, 1.0, 2.0, 4.0)
+FOLD_EXACT_KS = (64, 128, 256, 512)   # 2, 4, 8 and 16 statistics slots
+FOLD_BOUNDED_KS = (384,)              # the model's K: 12 slots, 1/K rounded
+FOLD_QKV_SHAPES = ((3, 17, 2, 64), (2, 5, 4, 128), (2, 17, 4, 256), (1, 9, 8, 512))  # (B, N, H, D): D a power of two
+FOLD_QKV_BOUNDED = ((2, 17, 3, 192), (2, 5, 6, 384))
+FOLD_KINDS = ("linear", "qkv", "gelu", "head")
+
+
+def _pow2(k: int) -> bool:
+    return k & (k - 1) == 0
+
+
+def fold_codes(M: int, N: int, K: int):
+    """(mu [M], sigma [M], c [N]) fp64: neighbouring rows and columns 16 apart differ in code.
+    |mu| <= 11 for K a power of two, <= 4 otherwise (codes one apart then stay separated by
+    far more than :func:`fold_bound`); |c| <= 6."""
+    mod = 23 if _pow2(K) else 9
+    m, n = torch.arange(M, dtype=torch.float64), torch.arange(N, dtype=torch.float64)
+    mu = (5 * m) % mod - mod // 2
+    sigma = torch.tensor(FOLD_SIGMAS, dtype=torch.float64)[torch.arange(M) % 4]
+    return mu, sigma, (7 * n) % 13 - 6
+
+
+def fold_stats(mu, sigma, K: int) -> torch.Tensor:
+    """Row statistics [M, K/32, 2] fp32 with totals ``K mu`` and ``K (sigma^2 + mu^2)``, every
+    slot a distinct non-zero integer that also differs from the same slot of the next row: a
+    dropped, duplicated or neighbouring-row slot changes a total (asserted here)."""
+    M, NP = mu.shape[0], K // 32
+    assert K % 32 == 0 and 2 <= NP <= 16
+    tot = torch.stack((K * mu, K * (sigma * sigma + mu * mu)), dim=-1).tolist()  # [M, 2]
+    rows = []
+    for m in range(M):
+        comps = []
+        for k, (step, rstep, rmod) in enumerate(((3, 5, 7), (4, 7, 5))):
+            free = [step * j + rstep * (m % rmod) + 1 + k for j in range(NP - 1)]
+            prev = rows[-1][k] if rows else None
+            while True:  # the last slot closes the total; bump slot 0 until no two coincide
+                s = free + [tot[m][k] - sum(free)]
+                if len(set(s)) == NP and 0 not in s and (prev is None or all(x != y for x, y in zip(s, prev))):
+                    break
+                free[0] += 1
+            comps.append(s)
+        rows.append(comps)
+    st = torch.tensor(rows, dtype=torch.float64).transpose(1, 2).contiguous()   # [M, NP, 2]
+    assert bool((st == st.round()).all()) and float(st.abs().sum(1).max()) < EXACT_LIMIT and bool((st != 0).all())
+    want = torch.tensor(tot, dtype=torch.float64)
+    assert torch.equal(st.sum(1), want)
+    for k in range(2):
+        s = st[..., k]
+        srt = s.sort(dim=1).values
+        assert bool((srt[:, 1:] != srt[:, :-1]).all()), "fold_stats: two slots of a row coincide"
+        assert M == 1 or bool((s[1:] != s[:-1]).all()), "fold_stats: a slot equals the next row's"
+    return st.float()
+
+
+def fold_truth_exact(a, w, bias, mu, sigma, c, scale: int = 1):
+    """fp64 ``(a @ w.T - mu c) / sigma + bias`` of the probe, after asserting the exactness
+    condition on its own tensors: every value an integer / ``scale`` (a power of two), and
+    ``(K max|a| max|w| + max|mu c|) / min sigma + max|bias|``, on the scaled values, below 2^24."""
+    assert scale >= 1 and _pow2(scale)
+    K = a.shape[-1]
+    for t in (a, w, bias):
+        assert _is_int(t.double() * scale), "fold probe: operands must be integers / scale"
+    assert _is_int(mu) and _is_int(c) and _is_int(sigma * 2), "fold probe: codes must be integers, sigma dyadic"
+    bound = (K * _amax(a) * _amax(w) + _amax(mu) * _amax(c)) / float(sigma.min()) * scale * 2 + _amax(bias) * scale
+    assert bound < EXACT_LIMIT, f"exactness condition violated: {bound:.0f} >= 2^24 (K = {K})"
+    acc = a.double().cpu() @ w.double().cpu().t()
+    y = (acc - mu.unsqueeze(1) * c.unsqueeze(0)) / sigma.unsqueeze(1) + bias.double().cpu()
+    return y, acc
+
+
+def fold_bound(acc, mu, sigma, c):
+    """K not a power of two: the host's 1/K, hence mean and var, carry an fp32 rounding:
+    ``2^-22 (1 + mu^2/sigma^2) |acc - mu c| / sigma + 2^-22 |mu c| / sigma`` per element."""
+    mc = mu.unsqueeze(1) * c.unsqueeze(0)
+    s = sigma.unsqueeze(1)
+    return 2.0 ** -22 * ((1 + (mu / sigma).pow(2)).unsqueeze(1) * (acc - mc).abs() + mc.abs()) / s
+
+
+def _fold_report(got, want, acc, mu, sigma, c, bias, bad, first: int = 4) -> str:
+    """Which (row code, column code) the observed values decode to."""
+    lines = []
+    g = got.double().cpu()
+    for r, col in bad[:first].tolist():
+        if not bool(torch.isfinite(g[r, col])):
+            lines.append(f"  [{r}, {col}] got {float(g[r, col])!r} want {float(want[r, col])!r}")
+            continue
+        t = float(acc[r, col] - (g[r, col] - float(bias[col])) * sigma[r])  # the mean * c the value shows
+        line = f"  [{r}, {col}] got {float(g[r, col])!r} want {float(want[r, col])!r}: shows mean * c = {t:g}, " \
+               f"expected {float(mu[r]):g} * {float(c[col]):g}"
+        if c[col] != 0 and t / float(c[col]) == round(t / float(c[col])):
+            rows = (mu == t / float(c[col])).nonzero().flatten()[:4].tolist()
+            line += f"; with this column's c the mean code {t / float(c[col]):g} (rows {rows})"
+        if mu[r] != 0 and t / float(mu[r]) == round(t / float(mu[r])):
+            cols = (c == t / float(mu[r])).nonzero().flatten()[:4].tolist()
+            line += f"; with this row's mean the column code {t / float(mu[r]):g} (columns {cols})"
+        lines.append(line)
+    return "\n".join(lines)
+
+
+def assert_fold(got, y, acc, mu, sigma, c, bias, K: int, name: str = "", tile=None):
+    """``got`` ([M, N] GEMM rows) against the probe's truth ``y``: bit for bit for K a power of
+    two; otherwise between the roundings (to the output type: rounding is monotonic) of
+    ``y -/+`` :func:`fold_bound`.  A mismatch is decoded (:func:`_fold_report`)."""
+    got = got.cpu()
+    if _pow2(K):
+        truth = y.to(got.dtype)
+        bad = mismatches(got, truth)
+        if bad.shape[0] == 0:
+            return
+        try:
+            assert_exact(got, truth, name, tile, 0)
+        except AssertionError as e:
+            raise AssertionError(str(e) + "\n" + _fold_report(got, y, acc, mu, sigma, c, bias, bad)) from None
+    bnd = fold_bound(acc, mu, sigma, c)
+    lo, hi = (y - bnd).to(got.dtype).double(), (y + bnd).to(got.dtype).double()
+    g = got.double()
+    bad = (~((g >= lo) & (g <= hi))).nonzero()  # NaN counts as a mismatch
+    assert bad.shape[0] == 0, f"{name}: {bad.shape[0]} of {got.numel()} elements outside the operand bound\n" + \
+        _fold_report(got, y, acc, mu, sigma, c, bias, bad)
+
+
+def assert_fold_stats(mean, rstd, mu, sigma, K: int, name: str = ""):
+    """The returned ``ln_mean`` / ``ln_rstd``: bit for bit (K a power of two), else within
+    2^-22 |mu| and 2^-22 (1 + mu^2 / sigma^2) / sigma."""
+    if _pow2(K):
+        assert_exact(rstd.cpu(), (1.0 / sigma).float(), name + " ln_rstd (the reciprocal square root at 1/4, 1, 4, 16)")
+        assert_exact(mean.cpu(), mu.float(), name + " ln_mean")
+        return
+    em, er = (mean.double().cpu() - mu).abs(), (rstd.double().cpu() - 1.0 / sigma).abs()
+    assert bool((em <= 2.0 ** -22 * mu.abs()).all()), f"{name} ln_mean: max err {float(em.max()):.3e}"
+    assert bool((er <= 2.0 ** -22 * (1 + (mu / sigma).pow(2)) / sigma).all()), f"{name} ln_rstd: max err {float(er.max()):.3e}"
+
+
+def run_fold_consumer(kind: str, M: int, N: int, K: int, device, tile=None, geom=None, seed: int = 13):
+    """A LayerNorm-fold consumer on the constructed-statistics probe, once with random
+    integer ``a`` and once with ``a = 0`` (the output ``-mu_m c_n / sigma_m + b_n`` then names
+    both indices).  ``kind``: ``linear`` (bf16 and f32), ``qkv`` (``geom`` = (B, tokens, H);
+    N = 3 K), ``gelu`` (``u``), ``head`` (``geom`` = (B, C, H, W, p); ``head_fwd`` and
+    ``head_step_`` mode 2, weights and bias / 8).  Returned statistics and ``head_step_``'s ``x``
+    sit in canaries; ``ln_rstd`` is asserted before any output."""
+    ops, g = _ops(), _gen(seed)
+    head = kind == "head"
+    scale = 8 if head else 1
+    w = int_operands((N, K), -2 * scale, 2 * scale, g, torch.float32) / scale
+    b = int_operands((N,), -8 * scale, 8 * scale, g, torch.float32) / scale
+    mu, sigma, c = fold_codes(M, N, K)
+    st, cd = fold_stats(mu, sigma, K).to(device), c.float().to(device)
+    wd, bd = w.to(torch.bfloat16).to(device), b.to(device)
+    for pure in (False, True):
+        a = torch.zeros(M, K, dtype=torch.bfloat16) if pure else int_operands((M, K), -2, 2, g)
+        y, acc = fold_truth_exact(a, w, b, mu, sigma, c, scale)
+        ad = a.to(device)
+        name = f"fold {kind} M={M} N={N} K={K}{' a=0' if pure else ''}"
+        mean, mean_ok = canary((M,), 64, torch.float32, device)
+        rstd, rstd_ok = canary((M,), 64, torch.float32, device)
+        fold = (st, cd, 0.0, mean, rstd)
+        outs = []
+        if kind == "linear":
+            for f32 in (False, True):
+                outs.append((f"{name} {'f32' if f32 else 'bf16'}", ops.linear_fwd(ad, wd, bd, f32, fold=fold[:3])))
+            mean = None  # linear_fwd returns no statistics
+        elif kind == "qkv":
+            B, tokens, H = geom
+            assert B * tokens == M and N == 3 * K
+            outs.append((name, _qkv_rows(ops.qkv_fwd(ad, wd, bd, B, tokens, H, fold=fold))))
+        elif kind == "gelu":
+            outs.append((name + " u", ops.linear_gelu_fwd(ad, wd, bd, _rng(device), 9, 0.0, fold=fold)[0]))
+        elif head:
+            B, C, H, W, p = geom
+            assert B * ((H // p) * (W // p) + 1) == M and N == C * p * p
+            img = ops.head_fwd(ad, wd, bd, B, C, H, W, p, fold=fold)
+            x, x_ok = canary((B, C, H, W), 4 * W, torch.float32, device)
+            ops.head_step_(ad, wd, bd, x, None, None, p, 2, fold=fold[:3])
+        else:
+            raise ValueError(kind)
+        if mean is not None:
+            assert_fold_stats(mean, rstd, mu, sigma, K, name)
+            mean_ok(name + " ln_mean")
+            rstd_ok(name + " ln_rstd")
+        if head:
+            keep = (torch.arange(M) % (M // B) != 0).nonzero().flatten()  # cls rows are skipped
+            args = (y[keep], acc[keep], mu[keep], sigma[keep], c, b, K)
+            assert_fold(ops.image_to_rows(img, p), *args, name + " head_fwd", tile)
+            # clamp (monotonic, exact) applied to both sides of the comparison
+            rows = ops.image_to_rows(x, p).cpu()
+            inside = ((y[keep] > -1) & (y[keep] < 1)).double().mean().item()
+            assert pure or 0.01 < inside < 0.99, f"{name}: the probe does not exercise both sides of the clamp"
+            if _pow2(K):
+                assert_exact(rows, y[keep].clamp(-1.0, 1.0).float(), name + " head_step_ x", tile)
+            else:
+                unclamped = (rows.abs() < 1)
+                assert_fold(torch.where(unclamped, rows, y[keep].float()), *args, name + " head_step_ x", tile)
+            x_ok(name + " head_step_ x")
+        for nm, out in outs:
+            assert_fold(out, y, acc, mu, sigma, c, b, K, nm, tile)

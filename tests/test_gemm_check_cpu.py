@@ -105,6 +105,111 @@ def test_reference_passes_wgrad_probes():
         gc.run_wgrad_sq(gc.WGRAD_BIG_TOKENS, gc.WGRAD_BIG_SHAPES, CPU, store)
 
 
+def test_reference_passes_fold_consumer_probes():
+    """The constructed-statistics probe of the LayerNorm-fold consumers over the grid of
+    tests/test_gemm_exact_gpu.py section (h): mean, rstd and output exact for K a power of two
+    (which proves the exactness condition holds for the chosen codes), within the operand
+    bound at K = 192 / 384."""
+    shapes = set()
+    for bm, bn, _ in gc.TILES.values():
+        shapes |= {(M, N) for M in gc.edge_ms(bm) for N in gc.edge_ns(bn)}
+    for K in gc.FOLD_EXACT_KS + gc.FOLD_BOUNDED_KS:
+        for M, N in sorted(shapes):
+            for kind in ("linear", "gelu"):
+                gc.run_fold_consumer(kind, M, N, K, CPU)
+    for B, T, H, D in gc.FOLD_QKV_SHAPES + gc.FOLD_QKV_BOUNDED:
+        gc.run_fold_consumer("qkv", B * T, 3 * D, D, CPU, geom=(B, T, H))
+    for B, C, H, W, p, D in gc.HEAD_GEOMS:
+        gc.run_fold_consumer("head", B * ((H // p) * (W // p) + 1), C * p * p, D, CPU, geom=(B, C, H, W, p))
+
+
+def _fold_probe(M=145, N=136, K=256, seed=13):
+    g = torch.Generator().manual_seed(seed)
+    a, w = gc.int_operands((M, K), -2, 2, g), gc.int_operands((N, K), -2, 2, g)
+    b = gc.int_operands((N,), -8, 8, g, torch.float32)
+    mu, sigma, c = gc.fold_codes(M, N, K)
+    y, acc = gc.fold_truth_exact(a, w, b, mu, sigma, c)
+    return a, w, b, mu, sigma, c, gc.fold_stats(mu, sigma, K), y, acc
+
+
+def _fold_run(a, w, b, st, c, pure=False):
+    M = a.shape[0]
+    mean, rstd = torch.empty(M), torch.empty(M)
+    y = ref._lin(torch.zeros_like(a) if pure else a, w, b, st, c.float(), 0.0, mean, rstd)
+    return y, mean, rstd
+
+
+def test_fold_probe_exactness_condition_is_enforced():
+    a, w, b, mu, sigma, c, st, y, acc = _fold_probe()
+    out, mean, rstd = _fold_run(a, w, b, st, c)
+    gc.assert_fold(out, y, acc, mu, sigma, c, b, 256, "clean", TILE)
+    gc.assert_fold_stats(mean, rstd, mu, sigma, 256, "clean")
+    with pytest.raises(AssertionError, match="exactness"):  # codes too wide for fp32
+        gc.fold_truth_exact(a, w, b, mu * 4096, sigma, c * 4096)
+    with pytest.raises(AssertionError, match="integers"):
+        gc.fold_truth_exact(a, w, b, mu + 0.3, sigma, c)
+    with pytest.raises(AssertionError, match="integers / scale"):
+        gc.fold_truth_exact(a, w * 0.3, b, mu, sigma, c)
+    with pytest.raises(AssertionError):  # a total no fp32 slot sum holds exactly
+        gc.fold_stats(mu * 4096, sigma, 256)
+
+
+def test_mutant_fold_statistics_slot_dropped():
+    a, w, b, mu, sigma, c, st, y, acc = _fold_probe()
+    bad = st.clone()
+    bad[:, 5, 0] = 0  # slot 5 of the 8 sums never added (a butterfly step short)
+    out, mean, rstd = _fold_run(a, w, b, bad, c)
+    _rejects(lambda: gc.assert_fold_stats(mean, rstd, mu, sigma, 256, "m"))
+    _rejects(lambda: gc.assert_fold(out, y, acc, mu, sigma, c, b, 256, "m", TILE), "elements differ")
+    dup = st.clone()
+    dup[:, 5] = dup[:, 4]  # slot 4 read twice
+    _rejects(lambda: gc.assert_fold_stats(*_fold_run(a, w, b, dup, c)[1:], mu, sigma, 256, "m"))
+
+
+def test_mutant_fold_statistics_of_the_next_row():
+    a, w, b, mu, sigma, c, st, y, acc = _fold_probe()
+    nxt = torch.cat((st[1:], st[-1:]))  # row m reads the slots of row m + 1
+    out, mean, rstd = _fold_run(a, w, b, nxt, c, pure=True)
+    _rejects(lambda: gc.assert_fold_stats(mean, rstd, mu, sigma, 256, "m"), "ln_rstd")
+    y0, acc0 = gc.fold_truth_exact(torch.zeros_like(a), w, b, mu, sigma, c)
+    # sigma repeats every 4 rows: among rows of one sigma the pure-statistic probe names the row read
+    one = st.clone()
+    one[8] = st[12]
+    out = _fold_run(a, w, b, one, c, pure=True)[0]
+    _rejects(lambda: gc.assert_fold(out, y0, acc0, mu, sigma, c, b, 256, "m", TILE),
+             rf"\[8, \d+\] .* with this column's c the mean code {float(mu[12]):g} \(rows \[[\d, ]*\b12\b")
+    # a single slot of the next row in place of the row's own changes a total too
+    one = st.clone()
+    one[8, 3] = st[9, 3]
+    _rejects(lambda: gc.assert_fold_stats(*_fold_run(a, w, b, one, c)[1:], mu, sigma, 256, "m"))
+
+
+def test_mutant_fold_column_sums_shifted_16():
+    a, w, b, mu, sigma, c, st, y, acc = _fold_probe()
+    shifted = torch.roll(c, -16)  # c[n + 16] for c[n]
+    out, mean, rstd = _fold_run(a, w, b, st, shifted)
+    gc.assert_fold_stats(mean, rstd, mu, sigma, 256, "the statistics are right")
+    _rejects(lambda: gc.assert_fold(out, y, acc, mu, sigma, c, b, 256, "m", TILE),
+             rf"with this row's mean the column code {float(c[16]):g} \(columns \[[\d, ]*\b16\b")
+
+
+def test_fold_bound_separates_neighbouring_codes():
+    """K = 384: the operand bound is far below the change a mean code one off causes."""
+    a, w, b, mu, sigma, c, st, y, acc = _fold_probe(K=384)
+    assert float(mu.abs().max()) <= 4
+    out, mean, rstd = _fold_run(a, w, b, st, c)
+    gc.assert_fold(out, y, acc, mu, sigma, c, b, 384, "clean", TILE)
+    gc.assert_fold(out.bfloat16(), y, acc, mu, sigma, c, b, 384, "clean bf16", TILE)
+    gc.assert_fold_stats(mean, rstd, mu, sigma, 384, "clean")
+    step = (c.abs().unsqueeze(0) / sigma.unsqueeze(1))  # a mean code one off moves the output by |c| / sigma
+    bnd = gc.fold_bound(acc, mu, sigma, c)
+    assert float((bnd / step.clamp_min(1e-9))[:, c != 0].max()) < 1e-2
+    off = gc.fold_stats(mu + (torch.arange(mu.shape[0]) == 7), sigma, 384)
+    out = _fold_run(a, w, b, off, c)[0]
+    _rejects(lambda: gc.assert_fold(out, y, acc, mu, sigma, c, b, 384, "m", TILE), r"\[7, ")
+    _rejects(lambda: gc.assert_fold(out.bfloat16(), y, acc, mu, sigma, c, b, 384, "m", TILE), r"\[7, ")
+
+
 def test_exactness_condition_is_enforced():
     g = torch.Generator().manual_seed(0)
     a, w = gc.int_operands((4, 1152), -4, 4, g), gc.int_operands((8, 1152), -4, 4, g)

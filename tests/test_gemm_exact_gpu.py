@@ -20,8 +20,13 @@ the wide tile the tiles past the last whole round of CUs in up to 6 K pieces eac
 A new tile configuration joins TILES in ops/gemm_check.py and with it the grids of
 sections (a) and (b) here.
 
-Out of scope (non-integer epilogue arithmetic, kept on the tolerance tests): the
-LayerNorm-fold consumers, HEADL, HEAD modes 1 / 4, GELU's ``h``."""
+The LayerNorm-fold consumers (section (h)) run a probe whose row statistics and column
+sums are constructed so that mean, variance and the reciprocal square root are exact too
+(ops/gemm_check.py ``run_fold_consumer``); at K = 192 / 384 the host's 1/K is rounded and
+the same probe is compared within a bound computed from the operands.
+
+Out of scope (non-integer epilogue arithmetic, kept on the tolerance tests): HEADL, HEAD
+modes 1 / 4, GELU's ``h``."""
 import pytest
 import torch
 
@@ -458,3 +463,62 @@ def test_engines_own_their_wgrad_tickets():
     a, b = (e.wgrad_tickets for e in engines)
     assert a.data_ptr() != b.data_ptr() and a.numel() == b.numel() == ops.WGRAD_TICKETS
     assert a.dtype == torch.int32 and not a.any() and not b.any()
+
+
+# ----------------------------------------------------------------------------- (h) LayerNorm-fold consumers
+FOLD_KS = gc.FOLD_EXACT_KS + gc.FOLD_BOUNDED_KS
+
+
+def test_fold_reciprocal_square_root_is_exact_at_probe_sigmas():
+    """The one assumption of the exact fold probe: the hardware reciprocal square root the
+    epilogue uses (``__builtin_amdgcn_rsqf``) returns exactly 2, 1, 1/2, 1/4 at 1/4, 1, 4, 16.
+    Measured on an MI355X: it does, at all four, so the probe keeps every sigma and compares
+    on raw bits (no sigma restricted, no truth rebuilt from the returned rstd).  Asserted here
+    through the returned ``ln_rstd``; every probe below asserts it again before its output."""
+    from ddim_cold_amd.ops import ln_check as lc
+    M, K = 64, 128
+    mu, sigma, c = gc.fold_codes(M, 3 * K, K)
+    mu = torch.zeros_like(mu)
+    mean, rstd = torch.empty(M, device=DEV), torch.empty(M, device=DEV)
+    a, w = torch.zeros(M, K, dtype=torch.bfloat16, device=DEV), torch.zeros(3 * K, K, dtype=torch.bfloat16, device=DEV)
+    ops.qkv_fwd(a, w, torch.zeros(3 * K, device=DEV), 1, M, 2,
+                fold=(gc.fold_stats(mu, sigma, K).to(DEV), c.float().to(DEV), 0.0, mean, rstd))
+    assert set(sigma.tolist()) == set(gc.FOLD_SIGMAS)
+    gc.assert_exact(rstd.cpu(), (1.0 / sigma).float(), "rsqf at sigma^2 in {1/4, 1, 4, 16}")
+    lc._log("exact fold probe: the hardware reciprocal square root is exact at 1/4, 1, 4 and 16 (ln_rstd = 2, 1, 1/2, "
+            "1/4 to the bit): every sigma kept, outputs compared on raw bits")
+
+
+@pytest.mark.parametrize("K", FOLD_KS)
+@pytest.mark.parametrize("cfg", ALL_TILES)
+@pytest.mark.parametrize("kind,epi", [("linear", gc.EPI_BF16), ("gelu", gc.EPI_GELU)])
+def test_fold_tile_edges(kind, epi, cfg, K):
+    """``ln_st[m][slot]``, ``ln_c[n]``, ``ln_mean[m]`` / ``ln_rstd[m]`` indexing over ragged row
+    and column tiles at 2, 4, 8, 16 (exact) and 12 (bounded) statistics slots."""
+    bm, bn, _ = gc.TILES[cfg]
+    with ops.gemm_tile(cfg):
+        for M in gc.edge_ms(bm):
+            for N in gc.edge_ns(bn):
+                tile = assert_plan(cfg, epi, M, N, K)
+                assert tile == (bm, bn)
+                if kind == "linear":
+                    assert_plan(cfg, gc.EPI_F32, M, N, K)
+                gc.run_fold_consumer(kind, M, N, K, DEV, tile=tile)
+
+
+@pytest.mark.parametrize("cfg", ALL_TILES)
+@pytest.mark.parametrize("B,N,H,D", gc.FOLD_QKV_SHAPES + gc.FOLD_QKV_BOUNDED)
+def test_fold_qkv_exact(cfg, B, N, H, D):
+    with ops.gemm_tile(cfg):
+        tile = assert_plan(cfg, gc.EPI_QKV, B * N, 3 * D, D)
+        assert tile == gc.TILES[cfg][:2]
+        gc.run_fold_consumer("qkv", B * N, 3 * D, D, DEV, tile=tile, geom=(B, N, H))
+
+
+@pytest.mark.parametrize("cfg", TILES_4W)
+@pytest.mark.parametrize("B,C,H,W,p,D", gc.HEAD_GEOMS)
+def test_fold_head_exact(cfg, B, C, H, W, p, D):
+    M = B * ((H // p) * (W // p) + 1)
+    with ops.gemm_tile(cfg):
+        tile = assert_plan(cfg, gc.EPI_HEAD, M, C * p * p, D)
+        gc.run_fold_consumer("head", M, C * p * p, D, DEV, tile=tile, geom=(B, C, H, W, p))

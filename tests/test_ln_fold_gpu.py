@@ -268,3 +268,61 @@ def test_ln_fold_kernel_bf16_weights():
     close(outs[0], exp[0], 0, 0, "wf")
     close(outs[1], exp[1], 1e-3, 1e-5, "c")
     close(outs[2], exp[2], 1e-3, 1e-5, "bf")
+
+
+# ----------------------------------------------------------------------------- against an fp64 truth
+# (ops/ln_check.py; the reference runs the same grids on the CPU in tests/test_ln_check_cpu.py)
+from ddim_cold_amd.ops import ln_check as lc
+
+
+@pytest.mark.parametrize("bf16_w", [False, True])
+@pytest.mark.parametrize("r", lc.FOLD_RS)
+@pytest.mark.parametrize("K", lc.FOLD_KS)
+def test_fold_consumers_off_centre_rows(K, r, bf16_w):
+    """Rows with |mean| / std = r: every folded consumer against fp64 LayerNorm + GEMM, the
+    folded reference as mirror; returned mean / rstd at the a-priori term bound.  The error
+    itself grows like sqrt(2 + r^2) (a design limit, asserted on the reference on the CPU)."""
+    lc.run_fold_consumers(K, r, bf16_w, DEV)
+
+
+@pytest.mark.parametrize("r", lc.FOLD_RS)
+def test_fold_head_off_centre_rows(r):
+    lc.run_fold_head(r, DEV)
+
+
+@pytest.mark.parametrize("K", lc.FOLD_KS)
+def test_fold_constant_rows_cancel(K):
+    """var = 0, rstd = eps^-1/2 ~ 316: ``c`` cancels exactly what the GEMM accumulated, so
+    the output is ``bf`` within 316 * 16 * 2^-24 * |v| * sum_k |wf|."""
+    lc.run_fold_constant_rows(K, DEV)
+
+
+def test_fold_producer_chain():
+    lc.run_fold_producer_chain(DEV)
+
+
+@pytest.mark.parametrize("K,bf16_w", lc.FOLD_EDGE_KS)
+def test_ln_fold_edges(K, bf16_w):
+    """Row counts that straddle the 8 / 16 rows of a workgroup across job boundaries, the
+    widest and narrowest K of each of the three load paths."""
+    lc.run_ln_fold_edges(K, bf16_w, DEV)
+
+
+@pytest.mark.parametrize("bf16_w", [False, True])
+def test_ln_fold_32_jobs(bf16_w):
+    lc.run_ln_fold_edges(128, bf16_w, DEV, rows=(lc.FOLD_EDGE_ROWS * 6)[:lc.FOLD_MAX_JOBS])
+
+
+def test_ln_fold_rejects_bad_tables():
+    def call(K, n):
+        ws = [torch.randn(8, K, device=DEV) for _ in range(n)]
+        v = [torch.randn(K, device=DEV) for _ in range(n)]
+        outs = [[torch.empty(8, K, dtype=torch.bfloat16, device=DEV) for _ in range(n)]] + \
+               [[torch.empty(8, device=DEV) for _ in range(n)] for _ in range(2)]
+        ops.ln_fold_(ws, v, v, [None] * n, *outs)
+        torch.cuda.synchronize()
+    with pytest.raises(RuntimeError):
+        call(516, 1)
+    with pytest.raises(RuntimeError):
+        call(128, lc.FOLD_MAX_JOBS + 1)
+    call(128, lc.FOLD_MAX_JOBS)
