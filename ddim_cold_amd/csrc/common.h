@@ -205,9 +205,13 @@ __device__ __forceinline__ float wave_max(float v) {
 // nn.GELU (ViT.py:80).  erff() costs ~40 vector instructions per element (range
 // split + an exp inside; the GELU GEMM epilogue ran ~31 VALU per MFMA in the PMC
 // table).  Abramowitz & Stegun 7.1.28: erf(z) = 1 - t^-16, t = 1 + a1 z + .. + a6 z^6
-// (z >= 0, |error| <= 3e-7), i.e. 6 FMAs, 4 squarings and one v_rcp; the lower tail
-// 1 - erf(z) = t^-16 comes out directly (no cancellation).  The error is three
-// orders of magnitude below the bf16 rounding of the stored activations.
+// (z >= 0), i.e. 6 FMAs, 4 squarings and one v_rcp; the lower tail 1 - erf(z) = t^-16
+// comes out directly (no cancellation).  Accuracy of Phi: the formula itself is good
+// to 1.5e-7 (3e-7 on erf); its fp32 evaluation adds the roundings of the 6 FMAs (16x
+// through the squarings), of the 4 squarings and of the reciprocal: 8.6e-7 at worst over
+// every bf16 input in an fp32 emulation (near x = 0.06), 3.4e-6 as the derived bound
+// (ops/epi_check.py, where tests/test_epi_values_gpu.py takes its 4e-6 from).  That
+// stays below half a bf16 ulp of the stored activation (2^-9 relative).
 __device__ __forceinline__ float norm_cdf(float x) {
   const float z = fabsf(x) * 0.70710678118654752f;
   float t = fmaf(z, 4.30638e-5f, 2.765672e-4f);

@@ -25,8 +25,9 @@ sums are constructed so that mean, variance and the reciprocal square root are e
 (ops/gemm_check.py ``run_fold_consumer``); at K = 192 / 384 the host's 1/K is rounded and
 the same probe is compared within a bound computed from the operands.
 
-Out of scope (non-integer epilogue arithmetic, kept on the tolerance tests): HEADL, HEAD
-modes 1 / 4, GELU's ``h``."""
+Out of scope here: the non-integer epilogue arithmetic (HEADL and HEAD mode 3, HEAD / HEADR
+modes 1 / 4, GELU's ``h``, GELU' in DGELU).  tests/test_epi_values_gpu.py checks it against
+fp64 truths with the value entering the epilogue set to the bit (ops/epi_check.py)."""
 import pytest
 import torch
 

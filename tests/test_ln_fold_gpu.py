@@ -230,11 +230,16 @@ def test_bf16_dgrad_into_layernorm_bwd(splits):
     close(gy, gyr, 1e-2, 1e-2, "gy")
 
 
-@pytest.mark.parametrize("B,C,H,W,p,D,fold", [(32, 3, 64, 64, 8, 384, True), (4, 3, 64, 64, 4, 256, False),
-                                              (3, 3, 32, 32, 8, 128, True)])
-def test_head_loss_fused(B, C, H, W, p, D, fold):
+@pytest.mark.parametrize("B,C,H,W,p,D,fold,beta", [
+    pytest.param(32, 3, 64, 64, 8, 384, True, 1.0, id="32-3-64-64-8-384-True"),
+    pytest.param(4, 3, 64, 64, 4, 256, False, 1.0, id="4-3-64-64-4-256-False"),
+    pytest.param(3, 3, 32, 32, 8, 128, True, 1.0, id="3-3-32-32-8-128-True"),
+    pytest.param(3, 3, 32, 32, 8, 128, True, 0.5, id="3-3-32-32-8-128-True-beta0.5"),
+    pytest.param(4, 3, 64, 64, 4, 256, False, 0.5, id="4-3-64-64-4-256-False-beta0.5")])
+def test_head_loss_fused(B, C, H, W, p, D, fold, beta):
     """Head GEMM with the smooth-L1 loss + token-layout gradient in its epilogue ==
-    head_fwd + smooth_l1_fwd_bwd."""
+    head_fwd + smooth_l1_fwd_bwd, also away from beta = 1 (where ``d / beta`` and ``d beta``,
+    ``|d| - beta / 2`` and ``|d| - 1/2`` coincide)."""
     N = (H // p) * (W // p) + 1
     M = B * N
     F = C * p * p
@@ -247,9 +252,9 @@ def test_head_loss_fused(B, C, H, W, p, D, fold):
         bf = torch.randn(F, device=DEV) * 0.1
         fk = None
     target = torch.randn(B, C, H, W, device=DEV).clamp(-1, 1)
-    parts, dtok = ops.head_loss(a, wf, bf, target, p, 1.0, fold=fk)
+    parts, dtok = ops.head_loss(a, wf, bf, target, p, beta, fold=fk)
     img = ops.head_fwd(a, wf, bf, B, C, H, W, p, fold=fk)
-    loss_r, dtok_r = ops.smooth_l1_fwd_bwd(img, target, N, p, 1.0)
+    loss_r, dtok_r = ops.smooth_l1_fwd_bwd(img, target, N, p, beta)
     torch.testing.assert_close(parts.sum(), loss_r.reshape(()), rtol=1e-4, atol=1e-6)
     close(dtok, dtok_r, 1e-6, 1e-2, "token-layout gradient")
     assert torch.count_nonzero(dtok.view(B, N, F)[:, 0]) == 0
