@@ -61,6 +61,45 @@ __device__ __forceinline__ bf16x8 frag_t(const char* lds, int c0, int s, int lan
   return v;
 }
 
+// ----------------------------------------------------------------------------- write-through stores
+// Output stores that go through L2 to memory as they are issued (sc1), so a kernel leaves
+// no dirty lines for the write-back at its end.  Same bytes, same addresses, same lanes as
+// the plain stores they replace; p is aligned to the store size.  4 and 8 bytes are relaxed
+// agent-scope atomic stores (global_store_dword/dwordx2 ... sc1); no builtin gives a 16-byte
+// store through a per-lane pointer, so that one is inline asm, closed by the wait states a
+// wide store needs before its data registers are written again.  -DDC_STORE_WT=0 compiles
+// them to plain stores (A/B of two builds).
+// Kept where the launch measured faster (profiles/store_writethrough.txt): the LayerNorm
+// backward and the short attention forward, whose waves write whole rows or 4-8 bytes per
+// lane.  The GEMM epilogues got SLOWER with them (16 rows x 32-64 bytes per wave instruction:
+// partial lines that a write-back L2 merges), AdamW, the fold and the short attention
+// backward showed no gain: all plain, so st_wt16 has no caller at present.
+#ifndef DC_STORE_WT
+#define DC_STORE_WT 1
+#endif
+__device__ __forceinline__ void st_wt4(void* p, uint32_t v) {
+#if DC_STORE_WT
+  __hip_atomic_store(reinterpret_cast<uint32_t*>(p), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#else
+  *reinterpret_cast<uint32_t*>(p) = v;
+#endif
+}
+__device__ __forceinline__ void st_wt8(void* p, u32x2 v) {
+#if DC_STORE_WT
+  __hip_atomic_store(reinterpret_cast<uint64_t*>(p), __builtin_bit_cast(uint64_t, v), __ATOMIC_RELAXED,
+                     __HIP_MEMORY_SCOPE_AGENT);
+#else
+  *reinterpret_cast<u32x2*>(p) = v;
+#endif
+}
+__device__ __forceinline__ void st_wt16(void* p, u32x4 v) {
+#if DC_STORE_WT
+  asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(p), "v"(v) : "memory");
+#else
+  *reinterpret_cast<u32x4*>(p) = v;
+#endif
+}
+
 // ----------------------------------------------------------------------------- RNG
 __host__ __device__ __forceinline__ uint32_t mix32(uint32_t x) {
   x ^= x >> 16;

@@ -9,7 +9,7 @@
 //   * the *next* residual branch's gradient prep  gy = bf16(g_out * dropout
 //     mask * drop-path scale)  (masks regenerated from the counter hash),
 //   * dgamma/dbeta column partials, deterministic: reduced per workgroup through
-//     LDS into a slot of its own (one row of the workspace, plain stores); a later
+//     LDS into a slot of its own (one row of the workspace); a later
 //     launch (replica_reduce, the embedding backward or the weight-gradient launch)
 //     sums the slots in slot order.  No fp32 atomics: two runs are bit-identical.
 //     (An in-launch reduction -- write-through slots, an agent-scope ticket, the
@@ -194,14 +194,17 @@ __global__ __launch_bounds__(NW * 64) void ln_bwd_kernel(const void* __restrict_
         const int c = lane + 64 * i;
         const float2 r = g_res ? rv[j][i] : make_float2(0.f, 0.f);
         float2 o = make_float2((dxh[i].x - c1 - xh[i].x * c2) * rs + r.x, (dxh[i].y - c1 - xh[i].y * c2) * rs + r.y);
-        reinterpret_cast<float2*>(g_out + (size_t)row * D)[c] = o;
+        // write-through (common.h st_wt*): the launch fell 6.0 -> 5.3 us at M 2,080, D 384
+        // (profiles/store_writethrough.txt)
+        st_wt8(reinterpret_cast<float2*>(g_out + (size_t)row * D) + c,
+               u32x2{__float_as_uint(o.x), __float_as_uint(o.y)});
         if (y_out) {
           // the LayerNorm output itself (bf16), for the weight gradient of the GEMM
           // that consumed it with the LayerNorm folded in (no forward LayerNorm launch)
           bf16x2 yv;
           yv[0] = f2bf(xh[i].x * gm[i].x + bt[i].x);
           yv[1] = f2bf(xh[i].y * gm[i].y + bt[i].y);
-          reinterpret_cast<bf16x2*>(y_out + (size_t)row * D)[c] = yv;
+          st_wt4(reinterpret_cast<bf16x2*>(y_out + (size_t)row * D) + c, __builtin_bit_cast(uint32_t, yv));
         }
         if (gy) {
           float a = o.x * dpsc, b = o.y * dpsc;
@@ -214,7 +217,7 @@ __global__ __launch_bounds__(NW * 64) void ln_bwd_kernel(const void* __restrict_
           bf16x2 h;
           h[0] = f2bf(a);
           h[1] = f2bf(b);
-          reinterpret_cast<bf16x2*>(gy + (size_t)row * D)[c] = h;
+          st_wt4(reinterpret_cast<bf16x2*>(gy + (size_t)row * D) + c, __builtin_bit_cast(uint32_t, h));
         }
         if (gprow) {  // patch-embedding input gradient (embedding dropout, same pair hash)
           float a = o.x, b = o.y;
@@ -226,13 +229,13 @@ __global__ __launch_bounds__(NW * 64) void ln_bwd_kernel(const void* __restrict_
           bf16x2 h;
           h[0] = f2bf(a);
           h[1] = f2bf(b);
-          reinterpret_cast<bf16x2*>(gprow)[c] = h;
+          st_wt4(reinterpret_cast<bf16x2*>(gprow) + c, __builtin_bit_cast(uint32_t, h));
         }
       }
     }
   }
-  // column partials: waves -> LDS -> this workgroup's slot (plain stores, summed in
-  // slot order by a later launch: deterministic, no atomics)
+  // column partials: waves -> LDS -> this workgroup's slot (summed in slot order by a
+  // later launch: deterministic, no atomics)
 #pragma unroll
   for (int i = 0; i < VEC; ++i) {
     const int c = 2 * (lane + 64 * i);
@@ -247,7 +250,7 @@ __global__ __launch_bounds__(NW * 64) void ln_bwd_kernel(const void* __restrict_
     float s = 0.f;
 #pragma unroll
     for (int w = 0; w < NW; ++w) s += red[w][c];
-    slot[c] = s;
+    st_wt4(slot + c, __float_as_uint(s));
   }
 }
 
