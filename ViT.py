@@ -37,10 +37,14 @@ from ddim_cold_amd.utils.images import get_next_path, save_grid, save_sequence_g
 @click.option("--seed", default=0)
 @click.option("--ema", is_flag=True, help="sample from the EMA weights: 'ema_state_dict' of a lastepoch.pkl-style "
               "--ckpt, else the <ckpt>_ema sibling file (bestloss.pkl -> bestloss_ema.pkl)")
-def main(sample_n, acc_k, ckpt, model_name, out_dir, seq_n, seq_k, seed, ema):
+@click.option("--eta", default=0.0, type=float, help="DDIM noise scale in [0, 1]: 0 deterministic DDIM (default), "
+              "1 DDPM ancestral sampling; applies to the trajectory grid and the samples")
+def main(sample_n, acc_k, ckpt, model_name, out_dir, seq_n, seq_k, seed, ema, eta):
     """DDIM sampling from a DiffusionVisionTransformer checkpoint."""
     from ddim_cold_amd.models import build_model
     from ddim_cold_amd.train.checkpoint import load_weights, resolve_ema_checkpoint
+    if not 0.0 <= eta <= 1.0:
+        sys.exit(f"error: --eta must be in [0, 1], got {eta}")
     device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
     model = build_model(model_name, init_order="vit")  # ViT.py:184 draw order (weights are loaded anyway)
     if ema:
@@ -56,9 +60,9 @@ def main(sample_n, acc_k, ckpt, model_name, out_dir, seq_n, seq_k, seed, ema):
         print(f"warning: {ckpt} not found, sampling from random-init weights", file=sys.stderr)
     model.to(device).eval()
     g = torch.Generator().manual_seed(seed)
-    seq = model.diffusion_sequence(device, seq_k, N=seq_n, generator=g)
+    seq = model.diffusion_sequence(device, seq_k, N=seq_n, generator=g, eta=eta)
     p1 = save_sequence_grid(seq, get_next_path(os.path.join(out_dir, "denoise_sequence.png")))
-    imgs = model.sampler(device, acc_k, sample_n, generator=g)
+    imgs = model.sampler(device, acc_k, sample_n, generator=g, eta=eta)
     p2 = save_grid(imgs, get_next_path(os.path.join(out_dir, "samples.png")), nrow=16)
     print(f"wrote {p1} and {p2}")
 

@@ -427,7 +427,8 @@ void head_step_(Tensor a, Tensor w, Tensor b, Tensor x, c10::optional<Tensor> x0
 // contiguous 16-byte vector (the image-layout head_step_ scatters 4-byte pixels).
 void head_step_rows_(Tensor a, Tensor w, Tensor b, Tensor x, c10::optional<Tensor> x0_out,
                      c10::optional<Tensor> coef, int64_t batch, int64_t mode, c10::optional<Tensor> ln_st,
-                     c10::optional<Tensor> ln_c, double ln_eps, c10::optional<Tensor> patches_out) {
+                     c10::optional<Tensor> ln_c, double ln_eps, c10::optional<Tensor> patches_out,
+                     c10::optional<Tensor> rng, int64_t noise_site) {
   CHECK_IN(a, BF16); CHECK_IN(w, BF16); CHECK_IN(b, F32); CHECK_IN(x, F32);
   const c10::DeviceGuard guard(a.device());
   const int K = a.size(-1);
@@ -437,7 +438,12 @@ void head_step_rows_(Tensor a, Tensor w, Tensor b, Tensor x, c10::optional<Tenso
   TORCH_CHECK(B >= 1 && x.dim() == 2 && x.size(1) == F && x.size(0) % B == 0, "x must be [B*P, F]");
   const int NP = x.size(0) / B, N = NP + 1;
   TORCH_CHECK(a2.size(0) == (int64_t)B * N && b.numel() == F && F % 4 == 0, "head rows shapes");
-  TORCH_CHECK(mode == 1 || mode == 2 || mode == 4, "head_step_rows_: mode 1 (ddim), 2 (clamp) or 4 (per-sample ddim)");
+  // modes 5 / 6 (EPI_HEADRS): the stochastic DDIM step (eta > 0), x <- c2 x0 + dir (x - c0 x0) / c1 + sigma z
+  // from rows of 8 floats {c0, c1, c2, dir, sigma, 0, 0, 0} (5: one row, 6: one per sample); z = element
+  // (row, column) of randn_ over x at (rng, noise_site), drawn in the epilogue
+  const bool noisy = mode == 5 || mode == 6;
+  TORCH_CHECK(mode == 1 || mode == 2 || mode == 4 || noisy,
+              "head_step_rows_: mode 1 (ddim), 2 (clamp), 4 (per-sample ddim), 5 (ddim with noise) or 6 (per-sample, with noise)");
   GemmArgs g = nt_args(a2, w);
   g.C = x.data_ptr(); g.bias = b.data_ptr<float>();
   g.tokens = N; g.batch = B;
@@ -448,13 +454,25 @@ void head_step_rows_(Tensor a, Tensor w, Tensor b, Tensor x, c10::optional<Tenso
     TORCH_CHECK(x0_out->sizes() == x.sizes() && coef->numel() >= (mode == 4 ? 4 * B : 4), "x0_out / coef shapes");
     g.res = x.data_ptr<float>(); g.C2 = x0_out->data_ptr(); g.coef = coef->data_ptr<float>();
   }
+  if (noisy) {
+    TORCH_CHECK(x0_out.has_value() && coef.has_value(), "head_step_rows_: modes 5 / 6 need x0_out and coef");
+    TORCH_CHECK(rng.has_value() && rng->defined(), "head_step_rows_: modes 5 / 6 need rng ({seed, 0}) for the noise");
+    CHECK_IN((*x0_out), F32); CHECK_IN((*coef), F32); check_rng(*rng);
+    TORCH_CHECK(x0_out->sizes() == x.sizes(), "head_step_rows_: x0_out must have x's shape");
+    TORCH_CHECK(coef->numel() == (mode == 6 ? 8 * (int64_t)B : 8),
+                "head_step_rows_: modes 5 / 6 take coefficient rows of 8 floats (mode 5: 8, mode 6: 8 * B)");
+    TORCH_CHECK(x.numel() < (1LL << 31), "head_step_rows_: the noise index is 32-bit (B*P*F < 2^31)");
+    TORCH_CHECK(noise_site >= 0 && noise_site < (1LL << 31), "head_step_rows_: noise_site out of range");
+    g.res = x.data_ptr<float>(); g.C2 = x0_out->data_ptr(); g.coef = coef->data_ptr<float>();
+    g.rng = rng->data_ptr<int64_t>(); g.site_drop = (int)noise_site;
+  }
   if (patches_out.has_value() && patches_out->defined()) {
     CHECK_IN((*patches_out), BF16);
     TORCH_CHECK(patches_out->sizes() == x.sizes(), "patches_out must be [B*P, F]");
     g.patch_out = patches_out->data_ptr();
   }
   apply_fold(g, B * N, F, ln_st, ln_c, ln_eps, c10::nullopt, c10::nullopt);
-  gemm_nt(g, EPI_HEADR, cur_stream());
+  gemm_nt(g, noisy ? EPI_HEADRS : EPI_HEADR, cur_stream());
 }
 
 // Head GEMM with the training loss in its epilogue (head_mode 3): the smooth-L1
@@ -1273,7 +1291,8 @@ TORCH_LIBRARY(ddim_cold, m) {
   m.def("head_step_(Tensor a, Tensor w, Tensor b, Tensor(a!) x, Tensor(b!)? x0_out, Tensor? coef, int patch, "
         "int mode, Tensor? ln_st=None, Tensor? ln_c=None, float ln_eps=1e-5, Tensor(c!)? patches_out=None) -> ()");
   m.def("head_step_rows_(Tensor a, Tensor w, Tensor b, Tensor(a!) x, Tensor(b!)? x0_out, Tensor? coef, int batch, "
-        "int mode, Tensor? ln_st=None, Tensor? ln_c=None, float ln_eps=1e-5, Tensor(c!)? patches_out=None) -> ()");
+        "int mode, Tensor? ln_st=None, Tensor? ln_c=None, float ln_eps=1e-5, Tensor(c!)? patches_out=None, "
+        "Tensor? rng=None, int noise_site=0) -> ()");
   m.def("head_loss(Tensor a, Tensor w, Tensor b, Tensor target, int patch, float beta, Tensor? ln_st=None, "
         "Tensor? ln_c=None, float ln_eps=1e-5, Tensor(a!)? ln_mean=None, Tensor(b!)? ln_rstd=None, "
         "bool target_rows=False) -> (Tensor, Tensor)");

@@ -313,6 +313,18 @@ __device__ __forceinline__ float gauss_eps(uint32_t nsalt, uint32_t o) {
   __sincosf(6.283185307179586f * b, &s, &c);
   return (o & 1u) ? r * s : r * c;
 }
+// Both outputs of the Box-Muller pair that holds elements e, e + 1 (e even) of randn_kernel's
+// draw at a site (nsalt = its site_salt): {r cos, r sin}.  randn_kernel's operations in its
+// order, so the values are its values bit for bit (the stochastic sampler's head epilogue
+// draws its noise with this: two pairs per lane's 4 columns).
+__device__ __forceinline__ float2 gauss_pair(uint32_t nsalt, uint32_t e) {
+  const float a = ((float)(mix32((e * 0x9E3779B1u) ^ nsalt) >> 8) + 0.5f) * (1.0f / 16777216.0f);
+  const float b = ((float)(mix32(((e + 1u) * 0x9E3779B1u) ^ nsalt) >> 8) + 0.5f) * (1.0f / 16777216.0f);
+  const float r = sqrtf(-2.f * __logf(a));
+  float s, c;
+  __sincosf(6.283185307179586f * b, &s, &c);
+  return make_float2(r * c, r * s);
+}
 __device__ __forceinline__ void gauss_coef(int t, int T, float& sa, float& s1a) {
   const float a = (float)(1.0 - sqrt(((double)t + 1.0) / (double)T));
   sa = sqrtf(a);

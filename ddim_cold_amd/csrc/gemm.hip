@@ -635,6 +635,7 @@ DC_INST_DMA3(EPI_HEAD)
 DC_INST_DMA3(EPI_EMBED) DC_INST_W8(false, false, EPI_EMBED)
 DC_INST_DMA3(EPI_HEADR)
 DC_INST_DMA3(EPI_HEADL)
+DC_INST_DMA3(EPI_HEADRS)
 DC_INST_DMA2(false, true, EPI_BF16) DC_INST_W8(false, true, EPI_BF16)
 DC_INST_DMA2(false, true, EPI_F32) DC_INST_W8(false, true, EPI_F32)
 DC_INST_DMA2(false, true, EPI_DGELU)
@@ -926,6 +927,13 @@ void gemm_nt(const GemmArgs& a, int epi, hipStream_t stream) {
     case EPI_HEADL:
       if (p.K % 64 != 0) throw std::runtime_error("gemm_nt: EPI_HEADL needs the LDS-DMA GEMM");
       launch_auto<false, false, EPI_HEADL>(p, 1, stream);
+      break;
+    case EPI_HEADRS:
+      if (p.K % 64 != 0) throw std::runtime_error("gemm_nt: EPI_HEADRS needs the LDS-DMA GEMM");
+      if ((p.head_mode != 5 && p.head_mode != 6) || p.rng == nullptr || p.coef == nullptr || p.res == nullptr ||
+          p.C2 == nullptr)
+        throw std::runtime_error("gemm_nt: EPI_HEADRS needs head mode 5 or 6 with rng, coef, x_t and x0_out");
+      launch_auto<false, false, EPI_HEADRS>(p, 1, stream);
       break;
     default: throw std::runtime_error("gemm_nt: unsupported epilogue");
   }

@@ -43,6 +43,9 @@ struct GemmParams {
                          //   3 training loss (res = target image, C2 = token-layout grad, loss_parts),
                          //   4 DDIM step with per-sample coefficients (img2img: a sample that has
                          //     not reached its start step has the row {0, 1, 0, 1}: x_next = x_t)
+                         // HEADRS: 5 stochastic DDIM step, coef = one row of 8 floats {c0, c1, c2, dir,
+                         //   sigma, 0, 0, 0}; 6 one such row per sample ([batch][8]; not started:
+                         //   {0, 1, 0, 1, 0, ..}).  rng = {seed, 0}, site_drop = the step's noise site
   float loss_beta;       // HEAD mode 3: smooth-L1 beta and 1/numel
   float loss_inv_n;
   float* loss_parts;     // HEAD mode 3: one loss partial per workgroup (gridDim.x entries)
@@ -158,7 +161,7 @@ template <int EPI>
 struct FoldEpi {
   static constexpr bool CONSUMER =
       EPI == EPI_QKV || EPI == EPI_GELU || EPI == EPI_BF16 || EPI == EPI_F32 || EPI == EPI_HEAD ||
-      EPI == EPI_HEADR || EPI == EPI_HEADL;
+      EPI == EPI_HEADR || EPI == EPI_HEADL || EPI == EPI_HEADRS;
   static constexpr bool PRODUCER = EPI == EPI_RESID || EPI == EPI_EMBED;
 };
 
@@ -211,6 +214,11 @@ __device__ __forceinline__ RowInfo32 epi_row32(const GemmParams& p, int m) {
     ri.b = m - b * p.tokens == 0 ? -1 : b;
   } else if (EPI == EPI_HEADR) {
     // token row m of sample b -> patch row b*P + tok - 1 = m - b - 1 (cls rows skipped)
+    const int b = divmagic(m, p.tokens, p.tok_magic), tok = m - b * p.tokens;
+    ri.off = tok == 0 ? -1 : (m - b - 1) * p.N;
+    ri.b = b;
+  } else if (EPI == EPI_HEADRS) {
+    // as HEADR; off + column is also the element's index in the step's noise draw
     const int b = divmagic(m, p.tokens, p.tok_magic), tok = m - b * p.tokens;
     ri.off = tok == 0 ? -1 : (m - b - 1) * p.N;
     ri.b = b;
@@ -507,6 +515,13 @@ __device__ __forceinline__ float2 stat4(const f32x4& v) {
                      __builtin_fmaf(v[0], v[0], v[1] * v[1]) + __builtin_fmaf(v[2], v[2], v[3] * v[3]));
 }
 
+// v as it stands in its register: the product or sum that made it is rounded on its own, the
+// compiler cannot fuse it into a multiply-add with an operation on either side of it
+__device__ __forceinline__ float rounded(float v) {
+  asm volatile("" : "+v"(v));
+  return v;
+}
+
 __device__ __forceinline__ void st2f(float* p, float2 v) { *reinterpret_cast<float2*>(p) = v; }
 __device__ __forceinline__ float2 ld2f(const float* p) { return *reinterpret_cast<const float2*>(p); }
 __device__ __forceinline__ f32x4 ld4bf(const bf16* p) {
@@ -534,10 +549,11 @@ __device__ __forceinline__ f32x4 ld4bf(const bf16* p) {
 template <int EPI, int FM, int FN, bool SW = false>
 struct VecEpi {
   static constexpr bool PRE = EPI == EPI_RESID || EPI == EPI_DGELU || EPI == EPI_EMBED || EPI == EPI_ACC ||
-                              EPI == EPI_HEADR || EPI == EPI_HEADL;
+                              EPI == EPI_HEADR || EPI == EPI_HEADL || EPI == EPI_HEADRS;
   static constexpr bool FC = FoldEpi<EPI>::CONSUMER, FP = FoldEpi<EPI>::PRODUCER;
   RowInfo32 rows[FM];
   f32x4 hcf[FM];    // HEADR: the row's DDIM coefficients {sqrt a_t, sqrt(1-a_t), sqrt a_tk, sqrt(1-a_tk)}
+  float hsg[FM];    // HEADRS: the row's sigma (hcf: its {c0, c1, c2, dir})
   int cols[FN];
   bool colok[FN];
   f32x4 colb[FN];
@@ -585,7 +601,7 @@ struct VecEpi {
     // load under the dropout condition was waited for on the spot (vmcnt(0): the
     // operand stages issued before it too -- tools/ub_gemm_stamps.py, first stage of
     // the vit_small_200 GELU GEMM 2.7 us vs 1.8 without dropout)
-    const int64_t* rp = (p.thr_drop || p.thr_dp) ? p.rng : kEpiNoRng;
+    const int64_t* rp = (EPI == EPI_HEADRS || p.thr_drop || p.thr_dp) ? p.rng : kEpiNoRng;
     const auto* rs4 = (const __attribute__((address_space(4))) int64_t*)(uintptr_t)rp;
     rng0 = rs4[0];
     rng1 = rs4[1];
@@ -630,6 +646,14 @@ struct VecEpi {
         hcf[i] = p.head_mode == 4 ? ld4(p.coef + 4 * rows[i].b)
                  : p.head_mode == 1 ? ld4(p.coef) : f32x4{0.f, 1.f, 0.f, 1.f};
     }
+    if (EPI == EPI_HEADRS) {  // rows of 8 floats: {c0, c1, c2, dir} and, in the second 16 bytes, sigma
+#pragma unroll
+      for (int i = 0; i < FM; ++i) {
+        const float* cr = p.coef + (p.head_mode == 6 ? 8 * rows[i].b : 0);
+        hcf[i] = ld4(cr);
+        hsg[i] = cr[4];
+      }
+    }
     cls_i = -1;
     cls_b = 0;
     if (EPI == EPI_EMBED && p.cls_src != nullptr) {
@@ -663,6 +687,7 @@ struct VecEpi {
         } else if (PRE && rows[i].off >= 0 && colok[j]) {
           const int n = nb + j * 16 + cs;
           if (EPI == EPI_HEADR && p.head_mode != 2) v = ld4(p.res + rows[i].off + n);  // x_t
+          if (EPI == EPI_HEADRS) v = ld4(p.res + rows[i].off + n);                      // x_t
           if (EPI == EPI_HEADL && rows[i].b >= 0)  // target patch row (m - b - 1)
             v = ld4(p.res + (rows[i].off - (rows[i].b + 1) * p.N) + n);
           if (EPI == EPI_ACC && !p.acc_store) v = ld4(reinterpret_cast<const float*>(p.C) + rows[i].off + n);
@@ -695,6 +720,8 @@ struct VecEpi {
     uint32_t salt_drop = 0, salt_dp = 0;
     if (p.thr_drop) salt_drop = site_salt_v((uint64_t)rng0, (uint64_t)rng1, p.site_drop);
     if (p.thr_dp) salt_dp = site_salt_v((uint64_t)rng0, (uint64_t)rng1, p.site_dp);
+    uint32_t salt_nz = 0;  // HEADRS: the step's noise site
+    if (EPI == EPI_HEADRS) salt_nz = site_salt_v((uint64_t)rng0, (uint64_t)rng1, p.site_drop);
     const bool fold = FC && p.ln_st != nullptr;
     const bool prod = FP && p.st_out != nullptr;
     float lsum = 0.f;  // HEADL: this lane's loss contributions
@@ -808,6 +835,36 @@ struct VecEpi {
             for (int c = 0; c < 4; ++c) xn[c] = cf[2] * x0[c] + cf[3] * ((pre[i][j][c] - cf[0] * x0[c]) / cf[1]);
             st4(reinterpret_cast<float*>(p.C2) + idx, x0);
           }
+          st4(reinterpret_cast<float*>(p.C) + idx, xn);
+          if (p.patch_out != nullptr) st4bf(p.patch_out + idx, xn);
+        } else if (EPI == EPI_HEADRS) {
+          // the DDIM family's step (eta > 0) on the patch rows: HEADR's update with the
+          // row's `dir` for sqrt(1-a_tk), plus sigma z.  z = elements idx..idx+3 of
+          // randn_kernel's draw over x at the step's site: the lane's 4 columns are two
+          // aligned Box-Muller pairs, both outputs of each used; drawn here, per fragment
+          f32x4 x0;
+#pragma unroll
+          for (int c = 0; c < 4; ++c) x0[c] = fminf(fmaxf(v[c], -1.f), 1.f);
+          const f32x4 cf = hcf[i];
+          const float sg = hsg[i];
+          const float2 z01 = gauss_pair(salt_nz, (uint32_t)idx), z23 = gauss_pair(salt_nz, (uint32_t)idx + 2u);
+          const f32x4 z = f32x4{z01.x, z01.y, z23.x, z23.y};
+          // The deterministic part with every rounding spelled out, so that a row with sigma = 0
+          // gives HEADR's bits (tests/test_ddim_eta_gpu.py holds that on every tile).  HEADR
+          // leaves the fusing of its statement to the compiler, which in every instantiation
+          // (4 tiles x 2 ring depths, read in their ISA) fuses x_t - c0 x0 everywhere, c2 x0 +
+          // (dir eps) in columns 0 and 1 (v_pk_fma_f32) and not in columns 2 and 3 (two products,
+          // v_pk_add_f32).  Left to the compiler here as well, the sum with the noise term was
+          // fused in all four columns: x differed from mode 1's in the last bit of ~1 % of the
+          // elements.
+          f32x4 xn;
+#pragma unroll
+          for (int c = 0; c < 4; ++c) {
+            const float de = rounded(cf[3] * (__builtin_fmaf(-cf[0], x0[c], pre[i][j][c]) / cf[1]));
+            const float det = c < 2 ? __builtin_fmaf(cf[2], x0[c], de) : rounded(cf[2] * x0[c]) + de;
+            xn[c] = __builtin_fmaf(sg, z[c], det);  // sigma = 0: det as it is
+          }
+          st4(reinterpret_cast<float*>(p.C2) + idx, x0);
           st4(reinterpret_cast<float*>(p.C) + idx, xn);
           if (p.patch_out != nullptr) st4bf(p.patch_out + idx, xn);
         } else if (EPI == EPI_EMBED) {

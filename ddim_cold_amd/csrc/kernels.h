@@ -21,6 +21,8 @@ enum GemmEpi : int {
                    //   in head-output column order (contiguous: vector epilogue)
   EPI_HEADL = 11,  // training loss on patch rows: smooth-L1 vs a [B*P][C*p*p] target (head order),
                    //   token-layout bf16 gradient, one loss partial per workgroup
+  EPI_HEADRS = 12, // EPI_HEADR's DDIM update with noise (eta > 0): x_next += sigma z, z drawn in the
+                   //   epilogue (randn_kernel's element at the destination index; rng, site_drop = site)
 };
 
 struct GemmArgs {
@@ -46,6 +48,7 @@ struct GemmArgs {
   int emb_dim = 0;
   const float* coef = nullptr;  // EPI_HEAD head_mode 1
   int head_mode = 0;            // EPI_HEAD: 0 image, 1 fused DDIM step, 2 clamp, 3 smooth-L1 loss + grad
+                                // EPI_HEADRS: 5 one 8-float row {c0, c1, c2, dir, sigma, 0, 0, 0}, 6 one per sample
   float loss_beta = 1.f;        // EPI_HEAD mode 3
   float loss_inv_n = 1.f;
   float* loss_parts = nullptr;  // EPI_HEAD mode 3: one partial per workgroup (gemm_nt_grid entries)

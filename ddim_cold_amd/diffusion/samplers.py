@@ -34,7 +34,8 @@ from typing import List, Optional, Sequence
 import torch
 
 from .. import ops
-from .schedule import cold_steps, ddim_coefficients, ddim_table, img2img_alpha
+from .schedule import (ETA_IDENT_ROW, cold_steps, ddim_coefficients, ddim_coefficients_eta, ddim_table,
+                       ddim_table_eta, eta_row, img2img_alpha)
 
 
 def _use_fused(model, device) -> bool:
@@ -153,9 +154,11 @@ class _Rows:
         self.x.copy_(ops.image_to_rows(x_img, self.p))
         self.pin.copy_(self.x)
 
-    def step(self, t, mode: int, coef=None):
+    def step(self, t, mode: int, coef=None, noise=None):
+        """``noise = (rng, site)`` (modes 5 / 6): the step's noise, drawn in the head epilogue."""
         x0 = None if mode == 2 else self.x0.view(self.shape)
-        self.den.step_(self.x.view(self.shape), t, mode, x0, coef, patches=(self.pin, self.pin, self.w))
+        patches = (self.pin, self.pin, self.w) if noise is None else (self.pin, self.pin, self.w, noise)
+        self.den.step_(self.x.view(self.shape), t, mode, x0, coef, patches=patches)
 
     def predict_x0(self, t):
         """One forward from the bf16 rows in ``pin`` with the clamp (mode 2) aimed at the
@@ -175,6 +178,50 @@ def _rows_state(model, N: int, device, den) -> Optional[_Rows]:
     if not (ROWS and PATCH_CHAIN and FUSED_HEAD and den.fused and torch.device(device).type == "cuda"):
         return None
     return _Rows(model, N, device, den)
+
+
+def _rows_state_eta(model, N: int, device, den) -> Optional[_Rows]:
+    """The patch-row state of a stochastic (eta > 0) loop: its step is a head mode of the
+    patch-row epilogue of the LayerNorm-folded program only (None: the fallback loop)."""
+    from ..models.program import fold_width_ok
+    if not (den.fused and den.P.folded and fold_width_ok(model.embed_dim)):
+        return None
+    return _rows_state(model, N, device, den)
+
+
+class _StepNoise:
+    """Noise of the stochastic samplers: step i adds ``sigma z_i`` with ``z_i`` = ``ops.randn_``
+    over the fp32 patch-row state [N*P, F] at ``rng = [seed, 0]``, site ``SITE_STEP_NOISE + i``
+    (so sample b's noise does not depend on the batch size).  ``rng`` is a static device
+    buffer the host writes before each run: a captured loop reads the seed from memory."""
+
+    def __init__(self, model, N: int, device):
+        p = model.patch_size
+        H, W = model.img_size
+        self.shape, self.p = (N, model.in_chans, H, W), p
+        self.rng = torch.zeros(2, dtype=torch.int64, device=device)
+        self.rows = (N * (H // p) * (W // p), model.in_chans * p * p)
+        self.z = None  # the fallback's rows-shaped draw (allocated on first use)
+
+    def site(self, i: int):
+        return (self.rng, ops.SITE_STEP_NOISE + i)
+
+    def set_seed(self, seed: int):
+        self.rng.copy_(torch.tensor([int(seed), 0], dtype=torch.int64))
+
+    def add_(self, x, i: int, sigma):
+        """Fallback (no fused epilogue): ``x += sigma z_i`` on the image-layout state; ``sigma``
+        a float or [N, 1, 1, 1]."""
+        if self.z is None:
+            self.z = torch.empty(self.rows, device=x.device)
+        ops.randn_(self.z, *self.site(i))
+        x.add_(ops.rows_to_image(self.z, *self.shape, self.p) * sigma)
+
+
+def draw_noise_seed(generator: Optional[torch.Generator] = None) -> int:
+    """One seed for a stochastic sampling run from ``generator`` (None: the global one)."""
+    dev = generator.device if generator is not None else "cpu"
+    return int(torch.randint(0, 2 ** 62, (1,), generator=generator, device=dev).item())
 
 
 def _chain_patches(pbuf, first: bool):
@@ -235,18 +282,35 @@ class _GraphLoop:
 
 
 class DDIMSampler:
-    def __init__(self, model, device, k: int = 10, use_graph: bool = True):
+    """DDIM sampler, jump ``k``.  ``eta`` in [0, 1] selects the member of the DDIM family
+    (Song et al. 2021): 0 the deterministic map from x_T (the default), 1 DDPM ancestral
+    sampling; ``eta`` > 0 adds ``sigma z`` per step (:func:`schedule.ddim_coefficients_eta`;
+    noise: :class:`_StepNoise`).  On the GPU's patch-row path a stochastic step is still ONE
+    forward: the head epilogue draws z in registers (``ops.head_step_rows_`` mode 5).  Elsewhere
+    (CPU, ``ROWS`` / ``FUSED_HEAD`` / ``PATCH_CHAIN`` off, the unfolded program) the
+    deterministic step is followed by ``ops.randn_`` and ``x += sigma z``: the same values up
+    to rounding, two more launches per step, no patch-row chain.
+
+    The seed of a run's noise is one ``torch.randint`` from ``generator`` after x_T is drawn
+    (``noise_seed=`` overrides it); with ``eta`` = 0 nothing extra is drawn."""
+
+    def __init__(self, model, device, k: int = 10, use_graph: bool = True, eta: float = 0.0):
         self.model = model
         self.device = torch.device(device)
         self.k = k
         self.T = model.total_steps
+        self.eta = float(eta)
+        ddim_coefficients_eta(self.T, self.T - 1, k, self.eta)  # (ValueError for eta outside [0, 1])
         self.ts, coef = ddim_table(self.T, k, device=self.device)
         self.coef = coef
+        self.coef8 = ddim_table_eta(self.T, k, self.eta, device=self.device)[1] if self.eta > 0 else None
         self.use_graph = use_graph and self.device.type == "cuda"
         self.H, self.W = model.img_size
         self.C = model.in_chans
 
     def _state(self, N: int, record: bool):
+        if self.eta > 0:
+            return self._state_eta(N, record)
         key = ("ddim", N, self.k, record, str(self.device))
         cache = _cache(self.model)
         st = cache.get(key)
@@ -281,9 +345,52 @@ class DDIMSampler:
         cache[key] = st
         return st
 
+    def _state_eta(self, N: int, record: bool):
+        """Buffers + loop of the stochastic sampler (its own cache key, eta included)."""
+        key = ("ddim_eta", N, self.k, record, str(self.device), self.eta)
+        cache = _cache(self.model)
+        st = cache.get(key)
+        if st is not None and st["key"] == _Denoiser.key_of(self.model):
+            return st
+        den = _Denoiser(self.model, self.device)
+        dev = self.device
+        x = torch.zeros(N, self.C, self.H, self.W, device=dev)
+        x0 = torch.zeros_like(x)
+        tt = torch.tensor(self.ts, dtype=torch.int64, device=dev).unsqueeze(1).expand(-1, N).contiguous()
+        traj = torch.zeros(len(self.ts), N, self.C, self.H, self.W, device=dev) if record else None
+        coef8 = self.coef8
+        coef4 = coef8[:, :4].contiguous()
+        sigma = [float(v) for v in coef8[:, 4].tolist()]
+        nz = _StepNoise(self.model, N, dev)
+        rs = _rows_state_eta(self.model, N, dev, den)
+
+        def loop():
+            if rs is not None:
+                rs.begin(x)
+                for i in range(len(self.ts)):
+                    rs.step(tt[i], 5, coef8[i], noise=nz.site(i))  # one forward: z drawn in the head epilogue
+                    if traj is not None:
+                        traj[i].copy_(rs.image(rs.x0))
+                x0.copy_(rs.image(rs.x0))
+                return
+            for i in range(len(self.ts)):
+                den.step_(x, tt[i], 1, x0, coef4[i])  # {c0, c1, c2, dir}: the deterministic part
+                nz.add_(x, i, sigma[i])
+                if traj is not None:
+                    traj[i].copy_(x0)
+
+        st = {"key": den.key(), "x": x, "x0": x0, "traj": traj, "noise": nz, "loop": _GraphLoop(loop, dev)}
+        cache[key] = st
+        return st
+
+    def _seed(self, st, generator, noise_seed):
+        if self.eta > 0:
+            st["noise"].set_seed(draw_noise_seed(generator) if noise_seed is None else noise_seed)
+
     @torch.no_grad()
     def sample(self, N: int, generator: Optional[torch.Generator] = None, verbose: bool = False,
-               noise: Optional[torch.Tensor] = None, device_noise: bool = False) -> torch.Tensor:
+               noise: Optional[torch.Tensor] = None, device_noise: bool = False,
+               noise_seed: Optional[int] = None) -> torch.Tensor:
         """``device_noise``: draw x_T on the GPU (``generator`` then a device generator)
         instead of on the host as the reference does (ViT.py:224-225) -- same
         distribution, a different stream; saves the host draw + copy (~2.5 ms per
@@ -296,6 +403,7 @@ class DDIMSampler:
             st["x"].normal_(0.0, 1.0, generator=generator)
         else:
             st["x"].copy_(torch.normal(0.0, 1.0, (N, self.C, self.H, self.W), generator=generator))
+        self._seed(st, generator, noise_seed)
         st["loop"].run(self.use_graph)
         out = _unit_host(st["x0"])
         if verbose:
@@ -304,11 +412,12 @@ class DDIMSampler:
 
     @torch.no_grad()
     def sequence(self, N: int, generator: Optional[torch.Generator] = None,
-                 noise: Optional[torch.Tensor] = None) -> List[torch.Tensor]:
+                 noise: Optional[torch.Tensor] = None, noise_seed: Optional[int] = None) -> List[torch.Tensor]:
         st = self._state(N, True)
         if noise is None:
             noise = torch.normal(0.0, 1.0, (N, self.C, self.H, self.W), generator=generator)
         st["x"].copy_(noise)
+        self._seed(st, generator, noise_seed)
         first = _unit_host(noise)
         st["loop"].run(self.use_graph)
         traj = _unit_host(st["traj"])
@@ -506,9 +615,58 @@ def starts_table(total_steps: int, starts: Sequence[int], k: int):
     return ts, torch.tensor(rows, dtype=torch.float32)
 
 
+def starts_table_eta(total_steps: int, starts: Sequence[int], k: int, eta: float):
+    """:func:`starts_table` for the DDIM family: rows of 8 floats ``{c0, c1, c2, dir, sigma,
+    0, 0, 0}`` ([len(ts), B, 8]); a sample that has not started has ``{0, 1, 0, 1, 0, 0, 0, 0}``
+    (x_next = x_t, no noise)."""
+    ts, _ = starts_table(total_steps, starts, k)
+    rows = [[eta_row(total_steps, t, k, eta) if s >= t else ETA_IDENT_ROW for s in starts] for t in ts]
+    return ts, torch.tensor(rows, dtype=torch.float32)
+
+
+def _from_starts_eta(model, B: int, starts, k: int, device, eta: float):
+    """Cached buffers + loop of :func:`ddim_from_starts` with ``eta`` > 0 (head mode 6)."""
+    key = ("img2img_eta", B, tuple(starts), k, str(device), float(eta))
+    cache = _cache(model)
+    st = cache.pop(key, None)
+    if st is not None:
+        cache[key] = st  # most recently used last
+    if st is not None and st["key"] == _Denoiser.key_of(model):
+        return st
+    cached = [c for c in cache if isinstance(c, tuple) and c[0] == "img2img_eta" and c != key]
+    for old in cached[:max(0, len(cached) - IMG2IMG_GRAPHS + 1)]:
+        del cache[old]
+    den = _Denoiser(model, device)
+    ts, coef8 = starts_table_eta(model.total_steps, starts, k, eta)
+    coef8 = coef8.to(device)
+    coef4 = coef8[:, :, :4].contiguous()
+    sigma = coef8[:, :, 4].reshape(len(ts), B, 1, 1, 1).contiguous()
+    xs = torch.zeros(B, model.in_chans, *model.img_size, device=device)
+    x0 = torch.zeros_like(xs)
+    tt = torch.tensor(ts, dtype=torch.int64, device=device).unsqueeze(1).expand(-1, B).contiguous()
+    nz = _StepNoise(model, B, device)
+    rs = _rows_state_eta(model, B, device, den)
+
+    def loop():
+        if rs is not None:
+            rs.begin(xs)
+            for i in range(len(ts)):
+                rs.step(tt[i], 6, coef8[i], noise=nz.site(i))
+            x0.copy_(rs.image(rs.x0))
+            xs.copy_(rs.image(rs.x))
+            return
+        for i in range(len(ts)):
+            den.step_(xs, tt[i], 4, x0, coef4[i])
+            nz.add_(xs, i, sigma[i])
+
+    st = {"key": den.key(), "x": xs, "x0": x0, "noise": nz, "loop": _GraphLoop(loop, device)}
+    cache[key] = st
+    return st
+
+
 @torch.no_grad()
 def ddim_from_starts(model, x: torch.Tensor, starts: Sequence[int], k: int, device=None,
-                     use_graph: bool = True) -> torch.Tensor:
+                     use_graph: bool = True, eta: float = 0.0, noise_seed: Optional[int] = None) -> torch.Tensor:
     """DDIM (jump ``k``) from per-sample start steps, all samples in ONE batch.
 
     Sample i joins the shared descending grid at its own ``starts[i]``; all starts
@@ -520,11 +678,24 @@ def ddim_from_starts(model, x: torch.Tensor, starts: Sequence[int], k: int, devi
     least recently used evicted).  Returns the final clamped x0-hat on the device,
     in [-1, 1], as a fresh tensor (not the graph's output buffer, which the next call
     with the same key overwrites).
+
+    ``eta`` > 0: the stochastic member of the DDIM family (see :class:`DDIMSampler`), head
+    mode 6 (per-sample rows of 8 coefficients, the noise drawn in the epilogue); a sample
+    that has not started is left exactly as it is.  ``noise_seed``: the run's noise seed
+    (None: one draw from the global generator).
     """
     device = torch.device(device) if device is not None else x.device
     T = model.total_steps
     B = x.shape[0]
     starts = [int(s) for s in starts]
+    eta = float(eta)
+    ddim_coefficients_eta(T, max(starts), k, eta)  # (ValueError for eta outside [0, 1])
+    if eta > 0:
+        st = _from_starts_eta(model, B, starts, k, device, eta)
+        st["x"].copy_(x.to(device).float())
+        st["noise"].set_seed(draw_noise_seed() if noise_seed is None else noise_seed)
+        st["loop"].run(use_graph and device.type == "cuda")
+        return st["x0"].clone()
     key = ("img2img", B, tuple(starts), k, str(device))
     cache = _cache(model)
     st = cache.pop(key, None)
@@ -563,7 +734,8 @@ def ddim_from_starts(model, x: torch.Tensor, starts: Sequence[int], k: int, devi
 
 @torch.no_grad()
 def img2img(model, draft: torch.Tensor, t_starts: Sequence[int] = tuple(range(1599, 2000, 50)), k: int = 10,
-            device=None, generator: Optional[torch.Generator] = None, use_graph: bool = True) -> torch.Tensor:
+            device=None, generator: Optional[torch.Generator] = None, use_graph: bool = True,
+            eta: float = 0.0) -> torch.Tensor:
     """Zero-shot draft->drawing (SDEdit-style) for several noise levels at once.
 
     For each t_start: x = sqrt(1-a) eps + sqrt(a) draft, a = 1 - sqrt(t_start/T)
@@ -573,7 +745,8 @@ def img2img(model, draft: torch.Tensor, t_starts: Sequence[int] = tuple(range(15
 
     All t_starts on one k-grid run as ONE batch, each sample joining the shared
     step grid at its own start (the reference loops them one at a time at batch
-    1); the loop is one cached hipGraph (:func:`ddim_from_starts`).
+    1); the loop is one cached hipGraph (:func:`ddim_from_starts`).  ``eta`` > 0: stochastic
+    DDIM steps (what SDEdit uses), their noise seed one more draw from ``generator``.
     """
     device = torch.device(device) if device is not None else next(model.parameters()).device
     T = model.total_steps
@@ -588,11 +761,12 @@ def img2img(model, draft: torch.Tensor, t_starts: Sequence[int] = tuple(range(15
     top = max(starts)
     if any((top - s) % k for s in starts):
         # different grids: run them one by one
-        return torch.cat([img2img(model, draft[i:i + 1], [s], k, device, generator, use_graph)
+        return torch.cat([img2img(model, draft[i:i + 1], [s], k, device, generator, use_graph, eta)
                           for i, s in enumerate(starts)])
     eps = torch.normal(0.0, 1.0, (B, C, H, W), generator=generator).to(device)
     x = img2img_noised(draft, eps, starts, T)
-    x0 = ddim_from_starts(model, x, starts, k, device, use_graph)
+    seed = draw_noise_seed(generator) if float(eta) > 0 else None
+    x0 = ddim_from_starts(model, x, starts, k, device, use_graph, eta, seed)
     return _unit_host(x0)
 
 

@@ -52,6 +52,50 @@ def ddim_table(total_steps: int, k: int, start: int | None = None, device="cpu")
     return ts, coef
 
 
+def ddim_coefficients_eta(total_steps: int, t: int, k: int, eta: float):
+    """``(c0, c1, c2, dir, sigma)`` of one jump of the DDIM family (Song et al. 2021, eq. 12
+    and 16): ``x_{t-k} = c2 x0 + dir (x_t - c0 x0) / c1 + sigma z`` with the ``a_t`` /
+    ``a_{t-k}`` of :func:`ddim_coefficients`,
+
+        ``sigma = eta sqrt((1 - a_{t-k}) / (1 - a_t) (1 - a_t / a_{t-k}))``,
+        ``dir = sqrt(1 - a_{t-k} - sigma^2)``.
+
+    ``eta`` = 0 is the deterministic sampler (the very floats of :func:`ddim_coefficients`,
+    ``sigma`` = 0.0), ``eta`` = 1 DDPM ancestral sampling.  At a last step onto ``a_{t-k}``
+    = 1 (k >= 2 dividing T) both ``sigma`` and ``dir`` are exactly 0."""
+    eta = float(eta)
+    if not 0.0 <= eta <= 1.0:  # (NaN fails too)
+        raise ValueError(f"eta must be in [0, 1], got {eta!r}")
+    c0, c1, c2, c3 = ddim_coefficients(total_steps, t, k)
+    if eta == 0.0:
+        return c0, c1, c2, c3, 0.0
+    a_t = 1.0 - math.sqrt((t + 1) / total_steps) + 1e-5
+    a_tk = 1.0 - math.sqrt((t + 1 - k) / total_steps)
+    rad = (1.0 - a_tk) / (1.0 - a_t) * (1.0 - a_t / a_tk)
+    if rad < 0.0:
+        raise ValueError(f"invalid DDIM jump t={t}, k={k}: a_t > a_(t-k)")
+    sigma = eta * math.sqrt(rad)
+    rdir = 1.0 - a_tk - sigma * sigma
+    if rdir < 0.0:
+        raise ValueError(f"invalid DDIM jump t={t}, k={k}, eta={eta}: 1 - a_(t-k) < sigma^2")
+    return c0, c1, c2, math.sqrt(rdir), sigma
+
+
+ETA_IDENT_ROW = (0.0, 1.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0)  # x_next = x_t: a sample that has not started
+
+
+def eta_row(total_steps: int, t: int, k: int, eta: float):
+    """The 8-float coefficient row ``{c0, c1, c2, dir, sigma, 0, 0, 0}`` of one jump."""
+    return ddim_coefficients_eta(total_steps, t, k, eta) + (0.0, 0.0, 0.0)
+
+
+def ddim_table_eta(total_steps: int, k: int, eta: float, start: int | None = None, device="cpu"):
+    """:func:`ddim_table` for the DDIM family: rows of 8 fp32 values (:func:`eta_row`)."""
+    ts = ddim_timesteps(total_steps, k, start)
+    coef = torch.tensor([eta_row(total_steps, t, k, eta) for t in ts], dtype=torch.float32, device=device)
+    return ts, coef
+
+
 def img2img_alpha(t_start: int, total_steps: int) -> float:
     return 1.0 - math.sqrt(t_start / total_steps)
 

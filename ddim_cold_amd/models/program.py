@@ -354,7 +354,7 @@ class ViTProgram:
         st = torch.empty(2 * L + 1, M, D // 32, 2, dtype=torch.float32, device=dev)
         xb = torch.empty(M, D, dtype=ACT_DTYPE, device=dev)
         # sampler steps: head_step = (mode, x0_out, coef, patches_in, patches_out[,
-        # pe_w_rows]); the previous step's head left this step's bf16 patch rows in
+        # pe_w_rows[, noise]]); the previous step's head left this step's bf16 patch rows in
         # patches_in.  With pe_w_rows the sampler state lives in patch rows
         # (ops.image_to_rows; ``img`` is a [B, C, H, W]-shaped view of that buffer):
         # the embedding reads the rows through the column-permuted weight and the
@@ -407,12 +407,15 @@ class ViTProgram:
         if head_step is not None:
             mode, x0_out, coef = head_step[:3]
             patches_out = head_step[4] if len(head_step) > 4 else None
+            noise = head_step[6] if len(head_step) > 6 else None  # modes 5 / 6: (rng, site) of the step's noise
             if rows_w is not None:
                 F = P.head_wf.shape[0]
                 ops.head_step_rows_(xb, P.head_wf, P.head_bf, img.view(-1, F),
                                     None if x0_out is None else x0_out.view(-1, F), coef, B, mode,
-                                    patches_out=patches_out, fold=(st[2 * L], P.head_c, c.eps))
+                                    patches_out=patches_out, fold=(st[2 * L], P.head_c, c.eps), noise=noise)
                 return img, S
+            if noise is not None:
+                raise ValueError("head modes 5 / 6 (noise in the head epilogue) need the patch-row sampler state")
             ops.head_step_(xb, P.head_wf, P.head_bf, img, x0_out, coef, c.patch, mode, patches_out=patches_out,
                            fold=(st[2 * L], P.head_c, c.eps))
             return img, S

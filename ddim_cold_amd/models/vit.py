@@ -333,17 +333,19 @@ class DiffusionVisionTransformer(nn.Module):
 
     # ------------------------------------------------------------------ samplers
     @torch.no_grad()
-    def sampler(self, device, k=10, N=128, generator=None, use_graph=True, verbose=False):
-        """DDIM k-step sampler (`ViT.py:220-237`); returns CPU images in [0, 1]."""
+    def sampler(self, device, k=10, N=128, generator=None, use_graph=True, verbose=False, eta=0.0):
+        """DDIM k-step sampler (`ViT.py:220-237`); returns CPU images in [0, 1].  ``eta`` in
+        [0, 1]: the DDIM family's noise scale (0: deterministic, 1: DDPM ancestral sampling)."""
         from ..diffusion.samplers import DDIMSampler
-        return DDIMSampler(self, device, k=k, use_graph=use_graph).sample(N, generator=generator,
-                                                                            verbose=verbose)
+        return DDIMSampler(self, device, k=k, use_graph=use_graph, eta=eta).sample(N, generator=generator,
+                                                                                     verbose=verbose)
 
     @torch.no_grad()
-    def diffusion_sequence(self, device, k=100, N=5, generator=None):
-        """DDIM trajectory recorder (`ViT.py:239-256`): [x_T, x0_hat_1, ...] on CPU."""
+    def diffusion_sequence(self, device, k=100, N=5, generator=None, eta=0.0):
+        """DDIM trajectory recorder (`ViT.py:239-256`): [x_T, x0_hat_1, ...] on CPU (``eta``
+        as in :meth:`sampler`)."""
         from ..diffusion.samplers import DDIMSampler
-        return DDIMSampler(self, device, k=k, use_graph=False).sequence(N, generator=generator)
+        return DDIMSampler(self, device, k=k, use_graph=False, eta=eta).sequence(N, generator=generator)
 
     @torch.no_grad()
     def cold_sampler(self, device, k=10, N=49, generator=None, use_graph=True, predict="prev", algorithm=2):

@@ -23,7 +23,7 @@ __all__ = [
     "linear_dgrad", "linear_dgrad_gelu", "linear_wgrad", "layernorm_bwd", "attn_bwd", "embed_bwd",
     "sqnorm", "adamw_step", "weight_ema_decay", "advance_counters", "ddim_step", "ddim_step_", "randn_", "q_sample",
     "pixelate_pair", "cold_batch", "gauss_batch", "head_step_rows_", "cold_step_", "cold_step_rows_",
-    "image_to_rows", "rows_to_image", "embed_weight_rows", "patch_embed_cold_fwd", "ln_fold_",
+    "image_to_rows", "rows_to_image", "embed_weight_rows", "patch_embed_cold_fwd", "ln_fold_", "SITE_STEP_NOISE",
 ]
 
 
@@ -231,12 +231,30 @@ def embed_weight_rows(w_pe, C: int, patch: int):
     return w_pe.reshape(D, C, patch, patch).permute(0, 2, 3, 1).reshape(D, C * patch * patch)
 
 
-def head_step_rows_(a, w, b, x, x0_out, coef, batch: int, mode: int, fold=None, patches_out=None):
+# noise site of sampling step i (0-based from the top of the grid): SITE_STEP_NOISE + i, clear
+# of the model's sites (1, 16 + 8 block + 0..5) and the data sites (3, 4)
+SITE_STEP_NOISE = 4096
+
+
+def head_step_rows_(a, w, b, x, x0_out, coef, batch: int, mode: int, fold=None, patches_out=None, noise=None):
     """:func:`head_step_` on patch rows (``x``/``x0_out``/``patches_out`` [B*P, F] in the
     head's output column order, :func:`image_to_rows`): every epilogue access is a
-    contiguous vector instead of a scattered pixel.  Same math per element."""
+    contiguous vector instead of a scattered pixel.  Same math per element.
+
+    Modes 5 / 6: the stochastic step of the DDIM family (eta > 0), ``x <- c2 x0 + dir (x -
+    c0 x0) / c1 + sigma z`` from coefficient rows of 8 floats ``{c0, c1, c2, dir, sigma, 0,
+    0, 0}`` (``schedule.eta_row``; mode 5 one row, mode 6 ``coef`` [B, 8], a sample that has
+    not started ``{0, 1, 0, 1, 0, ..}``).  ``noise = (rng, site)``: ``z`` is element (row,
+    column) of ``randn_(buf like x, rng, site)``, drawn inside the head epilogue on a GPU (no
+    noise buffer, no extra launch); ``rng`` a device int64[2] ``{seed, 0}``."""
     st, c, eps, _, _ = _fold_args(fold)
+    noisy = int(mode) in (5, 6)
+    if noisy != (noise is not None):
+        raise ValueError("head_step_rows_: modes 5 / 6 take noise=(rng, site), the other modes take none")
     if _hip(a):
+        if noisy:
+            return _ops().head_step_rows_(a, w, b, x, x0_out, coef, int(batch), int(mode), st, c, eps, patches_out,
+                                          noise[0], int(noise[1]))
         return _ops().head_step_rows_(a, w, b, x, x0_out, coef, int(batch), int(mode), st, c, eps, patches_out)
     F = w.shape[0]
     NP = x.shape[0] // batch
@@ -245,6 +263,16 @@ def head_step_rows_(a, w, b, x, x0_out, coef, batch: int, mode: int, fold=None, 
     x0 = torch.clamp(y, -1.0, 1.0)
     if mode == 2:
         x.copy_(x0)
+    elif noisy:
+        if coef.numel() != (8 * batch if mode == 6 else 8):
+            raise ValueError("head_step_rows_: modes 5 / 6 take coefficient rows of 8 floats")
+        z = torch.empty_like(x)
+        randn_(z, noise[0], int(noise[1]))
+        cf = coef.reshape(-1, 8).float()
+        cf = cf.repeat_interleave(NP, 0) if mode == 6 else cf.expand(x.shape[0], 8)
+        xn, _ = ref.ddim_step_eta(x, y, cf, z)
+        x.copy_(xn)
+        x0_out.copy_(x0)
     else:
         cf = coef.reshape(-1, 4).float()
         cf = cf.repeat_interleave(NP, 0) if cf.shape[0] == batch and mode == 4 else cf[:1].expand(x.shape[0], 4)

@@ -433,6 +433,36 @@ def ddim_step(x_t, x0_raw, coef):
     return sak * x0 + s1ak * eps, x0
 
 
+def ddim_coeffs_eta(total_steps: int, t: int, k: int, eta: float):
+    """``(c0, c1, c2, dir, sigma)`` of one jump of the DDIM family (``schedule.ddim_coefficients_eta``):
+    sigma = eta sqrt((1 - a_tk) / (1 - a_t) (1 - a_t / a_tk)), dir = sqrt(1 - a_tk - sigma^2)."""
+    if not 0.0 <= float(eta) <= 1.0:
+        raise ValueError(f"eta must be in [0, 1], got {eta!r}")
+    a_t = 1.0 - math.sqrt((t + 1) / total_steps) + 1e-5
+    a_tk = 1.0 - math.sqrt((t + 1 - k) / total_steps)
+    sigma = float(eta) * math.sqrt((1.0 - a_tk) / (1.0 - a_t) * (1.0 - a_t / a_tk))
+    return math.sqrt(a_t), math.sqrt(1.0 - a_t), math.sqrt(a_tk), math.sqrt(1.0 - a_tk - sigma * sigma), sigma
+
+
+def ddim_step_eta(x_t, x0_raw, coef8, z):
+    """One step of the DDIM family (fp32): ``x_next = c2 x0 + dir (x_t - c0 x0) / c1 + sigma z``
+    with ``x0 = clamp(x0_raw)``; returns (x_next, x0).  ``coef8``: ``(c0, c1, c2, dir, sigma,
+    ...)`` as floats or a tensor -- one row, or one row per leading index of ``x_t`` (a row per
+    sample of an image batch, or a row per patch row)."""
+    if isinstance(coef8, torch.Tensor):
+        cf = coef8.to(x_t.dtype).to(x_t.device)
+        if cf.dim() == 1:
+            c0, c1, c2, cd, sg = (cf[i] for i in range(5))
+        else:
+            shape = (-1,) + (1,) * (x_t.dim() - 1)
+            c0, c1, c2, cd, sg = (cf[:, i].reshape(shape) for i in range(5))
+    else:
+        c0, c1, c2, cd, sg = (float(v) for v in tuple(coef8)[:5])
+    x0 = torch.clamp(x0_raw, -1.0, 1.0)
+    eps = (x_t - c0 * x0) / c1
+    return c2 * x0 + cd * eps + sg * z, x0
+
+
 def pixelate(img, factor: int):
     """NEAREST down to floor(W/f) then NEAREST up (`diffusion_loader.py:79-83`)."""
     H, W = img.shape[-2:]
