@@ -26,14 +26,13 @@ chains on separate streams measured slower on MI355X -- ViT-tiny N=64 k=20:
 """
 from __future__ import annotations
 
-import math
-import os
 import time
 from typing import List, Optional, Sequence
 
 import torch
 
 from .. import ops
+from ..models.program import HeadStep, fold_width_ok, model_tensors
 from .schedule import (ETA_IDENT_ROW, cold_steps, ddim_coefficients, ddim_coefficients_eta, ddim_table,
                        ddim_table_eta, eta_row, img2img_alpha)
 
@@ -52,7 +51,6 @@ class _Denoiser:
         self.device = torch.device(device)
         self.fused = _use_fused(model, self.device)
         if self.fused:
-            from ..models.program import model_tensors
             self.prog = model.program()
             self.P = model_tensors(model)
             self.rng = torch.zeros(2, dtype=torch.int64, device=self.device)
@@ -70,30 +68,29 @@ class _Denoiser:
             return ("engine", id(eng))
         return tuple((p.data_ptr(), p._version) for p in model.parameters())
 
-    def step_(self, x, t, mode: int, x0_out=None, coef=None, patches=None):
+    def step_(self, x, t, hs: HeadStep):
         """In-place sampler step on ``x`` with the update fused into the head GEMM
-        (mode 1: DDIM with ``coef``, x0-hat into ``x0_out``; mode 2: clamp).
-        ``patches = (patches_in, patches_out)``: bf16 patch rows of ``x`` handed from
+        (``ops.HEAD_DDIM``: DDIM with ``hs.coef``, x0-hat into ``hs.x0_out``; ``ops.HEAD_CLAMP``:
+        clamp).  ``hs.patches_in`` / ``hs.patches_out``: bf16 patch rows of ``x`` handed from
         one step's head epilogue to the next step's patch embedding (no patchify
         launch per step; ``patches_in`` None on the first step)."""
-        if self.fused and FUSED_HEAD:
-            hs = (mode, x0_out, coef) if patches is None else (mode, x0_out, coef) + tuple(patches)
+        if self.fused:
             self.prog.forward(self.P, x, t, self.rng, False, save=False, head_step=hs)
             return
         x0_raw = self(x, t)
-        if mode == 2:
+        if hs.mode == ops.HEAD_CLAMP:
             torch.clamp(x0_raw, -1.0, 1.0, out=x)
         else:
-            ops.ddim_step_(x, x0_raw, x0_out, coef)
+            ops.ddim_step_(x, x0_raw, hs.x0_out, hs.coef)
 
-    def x0_(self, x, t, x0_out, ident, patches=None):
-        """Clamped x0-hat of f(x, t) into ``x0_out``; ``x`` is left exactly as it is (the
-        cold x0 sampler's forward: its update is :func:`ops.cold_step_`).  Fused: head
-        mode 1 with ``ident`` = the coefficient row {0, 1, 0, 1} (x_next = x_t)."""
-        if self.fused and FUSED_HEAD:
-            self.step_(x, t, 1, x0_out, ident, patches)
+    def x0_(self, x, t, hs: HeadStep):
+        """Clamped x0-hat of f(x, t) into ``hs.x0_out``; ``x`` is left exactly as it is (the
+        cold x0 sampler's forward: its update is :func:`ops.cold_step_`).  Fused: ``hs`` is
+        ``ops.HEAD_DDIM`` with the coefficient row {0, 1, 0, 1} (x_next = x_t)."""
+        if self.fused:
+            self.step_(x, t, hs)
             return
-        torch.clamp(self(x, t), -1.0, 1.0, out=x0_out)
+        torch.clamp(self(x, t), -1.0, 1.0, out=hs.x0_out)
 
     def __call__(self, x, t):
         if self.fused:
@@ -107,15 +104,15 @@ class _Denoiser:
             self.model.train(was)
 
 
-FUSED_HEAD = True  # module constants: tests switch them to compare the paths
-# the head epilogue of each step also writes the new x_t as the next step's bf16
+# module constants, read when a loop is built: tests switch them to compare the paths.
+# The head epilogue of each step also writes the new x_t as the next step's bf16
 # patch rows, so every step after the first skips the patchify launch
 PATCH_CHAIN = True
 
 
 def _patch_rows(model, N: int, device, den) -> Optional[torch.Tensor]:
     """bf16 [N*P, C*p*p] hand-off buffer for the patch-row chain (None: not used)."""
-    if not (PATCH_CHAIN and FUSED_HEAD and den.fused):
+    if not (PATCH_CHAIN and den.fused):
         return None
     p = model.patch_size
     H, W = model.img_size
@@ -136,7 +133,9 @@ class _Rows:
     Inside the loop: :meth:`begin` converts the [N, C, H, W] start image once and
     permutes the patch-embedding weight's columns into the head's order (so a
     replay after training uses the current weights); :meth:`step` is one forward
-    with the update in the head epilogue; :meth:`image` converts rows back."""
+    with the update in the head epilogue; :meth:`image` converts rows back and
+    :meth:`write_back` copies the state / x0-hat to the loop's image buffers."""
+    rows = True
 
     def __init__(self, model, N: int, device, den):
         p = model.patch_size
@@ -155,15 +154,15 @@ class _Rows:
         self.pin.copy_(self.x)
 
     def step(self, t, mode: int, coef=None, noise=None):
-        """``noise = (rng, site)`` (modes 5 / 6): the step's noise, drawn in the head epilogue."""
-        x0 = None if mode == 2 else self.x0.view(self.shape)
-        patches = (self.pin, self.pin, self.w) if noise is None else (self.pin, self.pin, self.w, noise)
-        self.den.step_(self.x.view(self.shape), t, mode, x0, coef, patches=patches)
+        """``noise = (rng, site)`` (``ops.HEAD_ETA`` / ``HEAD_ETA_EACH``): the step's noise, drawn
+        in the head epilogue."""
+        x0 = None if mode == ops.HEAD_CLAMP else self.x0.view(self.shape)
+        self.den.step_(self.x.view(self.shape), t, HeadStep(mode, x0, coef, self.pin, self.pin, self.w, noise))
 
     def predict_x0(self, t):
-        """One forward from the bf16 rows in ``pin`` with the clamp (mode 2) aimed at the
-        ``x0`` rows: ``x`` and ``pin`` stay as they are (the embedding reads only ``pin``)."""
-        self.den.step_(self.x0.view(self.shape), t, 2, patches=(self.pin, None, self.w))
+        """One forward from the bf16 rows in ``pin`` with the clamp aimed at the ``x0``
+        rows: ``x`` and ``pin`` stay as they are (the embedding reads only ``pin``)."""
+        self.den.step_(self.x0.view(self.shape), t, HeadStep(ops.HEAD_CLAMP, patches_in=self.pin, rows_w=self.w))
 
     def cold_step(self, t, algorithm: int):
         """``x`` <- cold step from ``x0`` (per-sample ``t``), and its bf16 rows into ``pin``."""
@@ -173,20 +172,86 @@ class _Rows:
     def image(self, xr):
         return ops.rows_to_image(xr, *self.shape, self.p)
 
+    def write_back(self, x=None, x0=None):
+        if x0 is not None:
+            x0.copy_(self.image(self.x0))
+        if x is not None:
+            x.copy_(self.image(self.x))
 
-def _rows_state(model, N: int, device, den) -> Optional[_Rows]:
-    if not (ROWS and PATCH_CHAIN and FUSED_HEAD and den.fused and torch.device(device).type == "cuda"):
-        return None
-    return _Rows(model, N, device, den)
+
+class _Image:
+    """Image-layout state of one sampling loop, with the interface of :class:`_Rows` (the
+    CPU, ``ROWS`` / ``PATCH_CHAIN`` off, a stochastic loop of the unfolded program): ``x`` and
+    ``x0`` are the loop's own [N, C, H, W] buffers (``x0`` None: one of its own), so nothing
+    is converted or copied back.  ``chain``: each step's head also writes the next step's
+    bf16 patch rows (:func:`_patch_rows`)."""
+    rows = False
+
+    def __init__(self, model, N: int, device, den, x, x0=None, chain: bool = True):
+        self.den, self.x = den, x
+        self.x0 = torch.zeros_like(x) if x0 is None else x0
+        self.pbuf = _patch_rows(model, N, device, den) if chain else None
+        self.ident = torch.tensor([0.0, 1.0, 0.0, 1.0], device=device)
+
+    def begin(self, x_img):
+        self.first = True  # (x_img is x)
+
+    def _head(self, mode: int, x0, coef) -> HeadStep:
+        pin, self.first = (None if self.first else self.pbuf), False  # the first step patchifies x itself
+        return HeadStep(mode, x0, coef, pin, self.pbuf)
+
+    def step(self, t, mode: int, coef=None):
+        self.den.step_(self.x, t, self._head(mode, None if mode == ops.HEAD_CLAMP else self.x0, coef))
+
+    def predict_x0(self, t):
+        """x0-hat into ``x0`` (:meth:`_Denoiser.x0_` with the identity row): ``x`` stays as it is."""
+        self.den.x0_(self.x, t, self._head(ops.HEAD_DDIM, self.x0, self.ident))
+
+    def cold_step(self, t, algorithm: int):
+        ops.cold_step_(self.x, self.x0, t, algorithm, patches_out=self.pbuf)
+
+    def image(self, xr):
+        return xr
+
+    def write_back(self, x=None, x0=None):
+        pass
 
 
-def _rows_state_eta(model, N: int, device, den) -> Optional[_Rows]:
-    """The patch-row state of a stochastic (eta > 0) loop: its step is a head mode of the
-    patch-row epilogue of the LayerNorm-folded program only (None: the fallback loop)."""
-    from ..models.program import fold_width_ok
-    if not (den.fused and den.P.folded and fold_width_ok(model.embed_dim)):
-        return None
-    return _rows_state(model, N, device, den)
+def _loop_state(model, N: int, device, den, x, x0=None, eta: bool = False):
+    """The state a loop steps: patch rows on the GPU's fused path, else the image layout on
+    the loop's buffers ``x`` / ``x0``.  ``eta``: a stochastic loop, whose step is a head mode
+    of the patch-row epilogue of the LayerNorm-folded program only; on the image layout its
+    noise changes ``x`` after the head wrote the bf16 rows, so there is no patch-row chain."""
+    rows = ROWS and PATCH_CHAIN and den.fused and torch.device(device).type == "cuda"
+    if rows and (not eta or (den.P.folded and fold_width_ok(model.embed_dim))):
+        return _Rows(model, N, device, den)
+    return _Image(model, N, device, den, x, x0, chain=not eta)
+
+
+def _ddim_step(s, coef, each: bool, nz):
+    """``step(i, t)`` of the DDIM family on the state ``s``: one forward with the update of
+    table row ``coef[i]`` in the head epilogue (``each``: one row per sample).  ``nz`` (eta > 0,
+    rows of 8): on patch rows still one forward, the noise drawn in the epilogue; on the image
+    layout the deterministic step on ``{c0, c1, c2, dir}`` followed by :meth:`_StepNoise.add_`."""
+    mode = ops.HEAD_DDIM_EACH if each else ops.HEAD_DDIM
+    if nz is None:
+        return lambda i, t: s.step(t, mode, coef[i])
+    if s.rows:
+        mode = ops.HEAD_ETA_EACH if each else ops.HEAD_ETA
+        return lambda i, t: s.step(t, mode, coef[i], noise=nz.site(i))
+    coef4 = coef[..., :4].contiguous()
+    sigma = coef[..., 4]  # per step a float, or [N, 1, 1, 1]
+    sigma = sigma.reshape(*sigma.shape, 1, 1, 1).contiguous() if each else [float(v) for v in sigma.tolist()]
+
+    def step(i, t):
+        s.step(t, mode, coef4[i])
+        nz.add_(s.x, i, sigma[i])
+    return step
+
+
+def _step_times(ts, N: int, device) -> torch.Tensor:
+    """[len(ts), N] int64: row i is step i's timestep for every sample."""
+    return torch.tensor(ts, dtype=torch.int64, device=device).unsqueeze(1).expand(-1, N).contiguous()
 
 
 class _StepNoise:
@@ -224,13 +289,6 @@ def draw_noise_seed(generator: Optional[torch.Generator] = None) -> int:
     return int(torch.randint(0, 2 ** 62, (1,), generator=generator, device=dev).item())
 
 
-def _chain_patches(pbuf, first: bool):
-    """(patches_in, patches_out) of one step: the first step patchifies x itself."""
-    if pbuf is None:
-        return None
-    return (None if first else pbuf, pbuf)
-
-
 def _unit_host(x: torch.Tensor) -> torch.Tensor:
     """(x + 1) / 2 as a host tensor -- the reference's return convention (ViT.py:236)
     -- with the affine done on the device before the copy: on the host it cost ~3 ms
@@ -243,6 +301,37 @@ def _unit_host(x: torch.Tensor) -> torch.Tensor:
 
 def _cache(model) -> dict:
     return model.__dict__.setdefault("_sampler_graphs", {})
+
+
+class _LoopState:
+    """One cached loop: its static buffers (``x`` in, ``x0`` / ``traj`` / ``x`` out), the
+    :class:`_StepNoise` of a stochastic one, the :class:`_GraphLoop`, and ``key`` = what the
+    capture depends on (:meth:`_Denoiser.key_of` when it was built)."""
+    __slots__ = ("key", "x", "x0", "traj", "noise", "loop")
+
+    def __init__(self, key, x, loop, x0=None, traj=None, noise=None):
+        self.key, self.x, self.x0, self.traj, self.noise, self.loop = key, x, x0, traj, noise, loop
+
+
+def _cached_loop(model, key, build, limit: Optional[int] = None) -> _LoopState:
+    """The model's loop under ``key`` (a tuple; ``key[0]`` names its kind), from ``build()`` if
+    there is none or the weights it captured were reallocated.  ``limit``: at most that many
+    loops of the kind stay cached, least recently used evicted."""
+    cache = _cache(model)
+    if limit is None:
+        st = cache.get(key)
+    else:
+        st = cache.pop(key, None)
+        if st is not None:
+            cache[key] = st  # most recently used last
+    if st is not None and st.key == _Denoiser.key_of(model):
+        return st
+    if limit is not None:
+        cached = [c for c in cache if isinstance(c, tuple) and c[0] == key[0] and c != key]
+        for old in cached[:max(0, len(cached) - limit + 1)]:
+            del cache[old]
+    st = cache[key] = build()
+    return st
 
 
 class _GraphLoop:
@@ -287,7 +376,7 @@ class DDIMSampler:
     sampling; ``eta`` > 0 adds ``sigma z`` per step (:func:`schedule.ddim_coefficients_eta`;
     noise: :class:`_StepNoise`).  On the GPU's patch-row path a stochastic step is still ONE
     forward: the head epilogue draws z in registers (``ops.head_step_rows_`` mode 5).  Elsewhere
-    (CPU, ``ROWS`` / ``FUSED_HEAD`` / ``PATCH_CHAIN`` off, the unfolded program) the
+    (CPU, ``ROWS`` / ``PATCH_CHAIN`` off, the unfolded program) the
     deterministic step is followed by ``ops.randn_`` and ``x += sigma z``: the same values up
     to rounding, two more launches per step, no patch-row chain.
 
@@ -309,83 +398,36 @@ class DDIMSampler:
         self.C = model.in_chans
 
     def _state(self, N: int, record: bool):
-        if self.eta > 0:
-            return self._state_eta(N, record)
+        """The cached buffers + loop (the stochastic sampler: its own kind of key, eta included)."""
         key = ("ddim", N, self.k, record, str(self.device))
-        cache = _cache(self.model)
-        st = cache.get(key)
-        if st is not None and st["key"] == _Denoiser.key_of(self.model):
-            return st
+        if self.eta > 0:
+            key = ("ddim_eta", N, self.k, record, str(self.device), self.eta)
+        return _cached_loop(self.model, key, lambda: self._build(N, record))
+
+    def _build(self, N: int, record: bool) -> _LoopState:
         den = _Denoiser(self.model, self.device)
         dev = self.device
         x = torch.zeros(N, self.C, self.H, self.W, device=dev)
         x0 = torch.zeros_like(x)
-        tt = torch.tensor(self.ts, dtype=torch.int64, device=dev).unsqueeze(1).expand(-1, N).contiguous()
+        tt = _step_times(self.ts, N, dev)
         traj = torch.zeros(len(self.ts), N, self.C, self.H, self.W, device=dev) if record else None
-        coef = self.coef
-        pbuf = _patch_rows(self.model, N, dev, den)
-        rs = _rows_state(self.model, N, dev, den)
+        nz = _StepNoise(self.model, N, dev) if self.eta > 0 else None
+        s = _loop_state(self.model, N, dev, den, x, x0, eta=nz is not None)
+        step = _ddim_step(s, self.coef if nz is None else self.coef8, False, nz)
 
         def loop():
-            if rs is not None:
-                rs.begin(x)
-                for i in range(len(self.ts)):
-                    rs.step(tt[i], 1, coef[i])
-                    if traj is not None:
-                        traj[i].copy_(rs.image(rs.x0))
-                x0.copy_(rs.image(rs.x0))  # (x_t itself is not returned)
-                return
+            s.begin(x)
             for i in range(len(self.ts)):
-                # forward + clamp + DDIM update, one head epilogue
-                den.step_(x, tt[i], 1, x0, coef[i], patches=_chain_patches(pbuf, i == 0))
+                step(i, tt[i])  # forward + clamp + DDIM update, one head epilogue
                 if traj is not None:
-                    traj[i].copy_(x0)
+                    traj[i].copy_(s.image(s.x0))
+            s.write_back(x0=x0)  # (x_t itself is not returned)
 
-        st = {"key": den.key(), "x": x, "x0": x0, "traj": traj, "loop": _GraphLoop(loop, dev)}
-        cache[key] = st
-        return st
-
-    def _state_eta(self, N: int, record: bool):
-        """Buffers + loop of the stochastic sampler (its own cache key, eta included)."""
-        key = ("ddim_eta", N, self.k, record, str(self.device), self.eta)
-        cache = _cache(self.model)
-        st = cache.get(key)
-        if st is not None and st["key"] == _Denoiser.key_of(self.model):
-            return st
-        den = _Denoiser(self.model, self.device)
-        dev = self.device
-        x = torch.zeros(N, self.C, self.H, self.W, device=dev)
-        x0 = torch.zeros_like(x)
-        tt = torch.tensor(self.ts, dtype=torch.int64, device=dev).unsqueeze(1).expand(-1, N).contiguous()
-        traj = torch.zeros(len(self.ts), N, self.C, self.H, self.W, device=dev) if record else None
-        coef8 = self.coef8
-        coef4 = coef8[:, :4].contiguous()
-        sigma = [float(v) for v in coef8[:, 4].tolist()]
-        nz = _StepNoise(self.model, N, dev)
-        rs = _rows_state_eta(self.model, N, dev, den)
-
-        def loop():
-            if rs is not None:
-                rs.begin(x)
-                for i in range(len(self.ts)):
-                    rs.step(tt[i], 5, coef8[i], noise=nz.site(i))  # one forward: z drawn in the head epilogue
-                    if traj is not None:
-                        traj[i].copy_(rs.image(rs.x0))
-                x0.copy_(rs.image(rs.x0))
-                return
-            for i in range(len(self.ts)):
-                den.step_(x, tt[i], 1, x0, coef4[i])  # {c0, c1, c2, dir}: the deterministic part
-                nz.add_(x, i, sigma[i])
-                if traj is not None:
-                    traj[i].copy_(x0)
-
-        st = {"key": den.key(), "x": x, "x0": x0, "traj": traj, "noise": nz, "loop": _GraphLoop(loop, dev)}
-        cache[key] = st
-        return st
+        return _LoopState(den.key(), x, _GraphLoop(loop, dev), x0, traj, nz)
 
     def _seed(self, st, generator, noise_seed):
         if self.eta > 0:
-            st["noise"].set_seed(draw_noise_seed(generator) if noise_seed is None else noise_seed)
+            st.noise.set_seed(draw_noise_seed(generator) if noise_seed is None else noise_seed)
 
     @torch.no_grad()
     def sample(self, N: int, generator: Optional[torch.Generator] = None, verbose: bool = False,
@@ -398,14 +440,14 @@ class DDIMSampler:
         st = self._state(N, False)
         t0 = time.time()
         if noise is not None:
-            st["x"].copy_(noise)
+            st.x.copy_(noise)
         elif device_noise:
-            st["x"].normal_(0.0, 1.0, generator=generator)
+            st.x.normal_(0.0, 1.0, generator=generator)
         else:
-            st["x"].copy_(torch.normal(0.0, 1.0, (N, self.C, self.H, self.W), generator=generator))
+            st.x.copy_(torch.normal(0.0, 1.0, (N, self.C, self.H, self.W), generator=generator))
         self._seed(st, generator, noise_seed)
-        st["loop"].run(self.use_graph)
-        out = _unit_host(st["x0"])
+        st.loop.run(self.use_graph)
+        out = _unit_host(st.x0)
         if verbose:
             print(f"ddim k={self.k} N={N}: {len(self.ts)} steps in {time.time() - t0:.3f}s")
         return out
@@ -416,11 +458,11 @@ class DDIMSampler:
         st = self._state(N, True)
         if noise is None:
             noise = torch.normal(0.0, 1.0, (N, self.C, self.H, self.W), generator=generator)
-        st["x"].copy_(noise)
+        st.x.copy_(noise)
         self._seed(st, generator, noise_seed)
         first = _unit_host(noise)
-        st["loop"].run(self.use_graph)
-        traj = _unit_host(st["traj"])
+        st.loop.run(self.use_graph)
+        traj = _unit_host(st.traj)
         return [first] + [traj[i] for i in range(traj.shape[0])]
 
 
@@ -459,15 +501,9 @@ class ColdSampler:
         key = ("cold", N, self.steps, str(self.device))
         if self.predict == "x0":
             key += ("x0", self.algorithm)
-        cache = _cache(self.model)
-        st = cache.get(key)
-        if st is not None and st["key"] == _Denoiser.key_of(self.model):
-            return st
-        st = self._build(N, [[t] * N for t in range(self.steps, 0, -1)])
-        cache[key] = st
-        return st
+        return _cached_loop(self.model, key, lambda: self._build(N, [[t] * N for t in range(self.steps, 0, -1)]))
 
-    def _build(self, N: int, levels):
+    def _build(self, N: int, levels) -> _LoopState:
         """Buffers + loop for the step grid ``levels`` ([steps][N], descending): row i holds
         the model's t of step i, or 0 for a sample that has not joined the grid yet (x0
         prediction only: the step kernel skips it)."""
@@ -475,54 +511,40 @@ class ColdSampler:
         dev = self.device
         x = torch.zeros(N, self.C, self.H, self.W, device=dev)
         ts = [max(row) for row in levels]
-        tt = torch.tensor(ts, dtype=torch.int64, device=dev).unsqueeze(1).expand(-1, N).contiguous()
+        tt = _step_times(ts, N, dev)
         traj = torch.zeros(len(ts), N, self.C, self.H, self.W, device=dev)
-        pbuf = _patch_rows(self.model, N, dev, den)
-        rs = _rows_state(self.model, N, dev, den)
+        s = _loop_state(self.model, N, dev, den, x)
         if self.predict == "x0":
-            loop = self._x0_loop(den, x, tt, torch.tensor(levels, dtype=torch.int64, device=dev), traj, pbuf, rs)
-            return {"key": den.key(), "x": x, "traj": traj, "loop": _GraphLoop(loop, dev)}
+            loop = self._x0_loop(s, x, tt, torch.tensor(levels, dtype=torch.int64, device=dev), traj)
+        else:
+            loop = self._prev_loop(s, x, tt, traj)
+        return _LoopState(den.key(), x, loop, traj=traj)
 
+    def _prev_loop(self, s, x, tt, traj) -> _GraphLoop:
         def loop():
-            if rs is not None:
-                rs.begin(x)
-                for i in range(len(ts)):
-                    rs.step(tt[i], 2)
-                    traj[i].copy_(rs.image(rs.x))
-                x.copy_(rs.image(rs.x))
-                return
-            for i in range(len(ts)):
-                # forward + clamp in the head epilogue
-                den.step_(x, tt[i], 2, patches=_chain_patches(pbuf, i == 0))
-                traj[i].copy_(x)
+            s.begin(x)
+            for i in range(tt.shape[0]):
+                s.step(tt[i], ops.HEAD_CLAMP)  # forward + clamp in the head epilogue
+                traj[i].copy_(s.image(s.x))
+            s.write_back(x=x)
 
-        return {"key": den.key(), "x": x, "traj": traj, "loop": _GraphLoop(loop, dev)}
+        return _GraphLoop(loop, self.device)
 
-    def _x0_loop(self, den, x, tt, tk, traj, pbuf, rs):
+    def _x0_loop(self, s, x, tt, tk, traj) -> _GraphLoop:
         """The x0-prediction loop: per step one forward (x0-hat into its own buffer, x
         untouched) and one cold-step launch with the per-sample levels ``tk[i]``; the
         recorded states and the final ``x`` are clamped to [-1, 1]."""
         alg = self.algorithm
-        x0 = torch.zeros_like(x) if rs is None else None
-        ident = torch.tensor([0.0, 1.0, 0.0, 1.0], device=x.device)
-        n = tt.shape[0]
 
         def loop():
-            if rs is not None:
-                rs.begin(x)
-                for i in range(n):
-                    rs.predict_x0(tt[i])
-                    rs.cold_step(tk[i], alg)
-                    torch.clamp(rs.image(rs.x), -1.0, 1.0, out=traj[i])
-                torch.clamp(rs.image(rs.x), -1.0, 1.0, out=x)
-                return
-            for i in range(n):
-                den.x0_(x, tt[i], x0, ident, patches=_chain_patches(pbuf, i == 0))
-                ops.cold_step_(x, x0, tk[i], alg, patches_out=pbuf)
-                torch.clamp(x, -1.0, 1.0, out=traj[i])
-            x.clamp_(-1.0, 1.0)
+            s.begin(x)
+            for i in range(tt.shape[0]):
+                s.predict_x0(tt[i])
+                s.cold_step(tk[i], alg)
+                torch.clamp(s.image(s.x), -1.0, 1.0, out=traj[i])
+            torch.clamp(s.image(s.x), -1.0, 1.0, out=x)
 
-        return loop
+        return _GraphLoop(loop, self.device)
 
     def _init(self, N, generator):
         c = torch.normal(0.0, 1.0, (N, self.C), generator=generator)
@@ -531,17 +553,17 @@ class ColdSampler:
     @torch.no_grad()
     def sample(self, N: int, generator=None) -> torch.Tensor:
         st = self._state(N)
-        st["x"].copy_(self._init(N, generator))
-        st["loop"].run(self.use_graph)
-        return _unit_host(st["x"])
+        st.x.copy_(self._init(N, generator))
+        st.loop.run(self.use_graph)
+        return _unit_host(st.x)
 
     @torch.no_grad()
     def sequence(self, N: int, generator=None) -> List[torch.Tensor]:
         st = self._state(N)
         init = self._init(N, generator)
-        st["x"].copy_(init)
-        st["loop"].run(self.use_graph)
-        traj = _unit_host(st["traj"])
+        st.x.copy_(init)
+        st.loop.run(self.use_graph)
+        traj = _unit_host(st.traj)
         return [(init + 1) / 2] + [traj[i] for i in range(traj.shape[0])]
 
     @torch.no_grad()
@@ -579,21 +601,13 @@ class ColdSampler:
             out = torch.clamp(start, -1.0, 1.0)
             return [to_host(out)] if sequence else to_host(out)
         key = ("cold_restore", B, tuple(levels), self.predict, self.algorithm, str(self.device))
-        cache = _cache(self.model)
-        st = cache.pop(key, None)
-        if st is not None:
-            cache[key] = st  # most recently used last
-        if st is None or st["key"] != _Denoiser.key_of(self.model):
-            cached = [c for c in cache if isinstance(c, tuple) and c[0] == "cold_restore" and c != key]
-            for old in cached[:max(0, len(cached) - COLD_RESTORE_GRAPHS + 1)]:
-                del cache[old]
-            st = self._build(B, [[t if v >= t else 0 for v in levels] for t in range(top, 0, -1)])
-            cache[key] = st
-        st["x"].copy_(start)
-        st["loop"].run(self.use_graph)
+        st = _cached_loop(self.model, key, lambda: self._build(
+            B, [[t if v >= t else 0 for v in levels] for t in range(top, 0, -1)]), COLD_RESTORE_GRAPHS)
+        st.x.copy_(start)
+        st.loop.run(self.use_graph)
         if not sequence:
-            return to_host(st["x"])
-        traj = to_host(st["traj"])
+            return to_host(st.x)
+        traj = to_host(st.traj)
         return [to_host(start)] + [traj[i] for i in range(traj.shape[0])]
 
 
@@ -624,44 +638,26 @@ def starts_table_eta(total_steps: int, starts: Sequence[int], k: int, eta: float
     return ts, torch.tensor(rows, dtype=torch.float32)
 
 
-def _from_starts_eta(model, B: int, starts, k: int, device, eta: float):
-    """Cached buffers + loop of :func:`ddim_from_starts` with ``eta`` > 0 (head mode 6)."""
-    key = ("img2img_eta", B, tuple(starts), k, str(device), float(eta))
-    cache = _cache(model)
-    st = cache.pop(key, None)
-    if st is not None:
-        cache[key] = st  # most recently used last
-    if st is not None and st["key"] == _Denoiser.key_of(model):
-        return st
-    cached = [c for c in cache if isinstance(c, tuple) and c[0] == "img2img_eta" and c != key]
-    for old in cached[:max(0, len(cached) - IMG2IMG_GRAPHS + 1)]:
-        del cache[old]
+def _from_starts_state(model, B: int, starts, k: int, device, eta: float) -> _LoopState:
+    """Buffers + loop of :func:`ddim_from_starts`."""
     den = _Denoiser(model, device)
-    ts, coef8 = starts_table_eta(model.total_steps, starts, k, eta)
-    coef8 = coef8.to(device)
-    coef4 = coef8[:, :, :4].contiguous()
-    sigma = coef8[:, :, 4].reshape(len(ts), B, 1, 1, 1).contiguous()
+    T = model.total_steps
+    ts, coef = starts_table_eta(T, starts, k, eta) if eta > 0 else starts_table(T, starts, k)
+    coef = coef.to(device)
     xs = torch.zeros(B, model.in_chans, *model.img_size, device=device)
     x0 = torch.zeros_like(xs)
-    tt = torch.tensor(ts, dtype=torch.int64, device=device).unsqueeze(1).expand(-1, B).contiguous()
-    nz = _StepNoise(model, B, device)
-    rs = _rows_state_eta(model, B, device, den)
+    tt = _step_times(ts, B, device)
+    nz = _StepNoise(model, B, device) if eta > 0 else None
+    s = _loop_state(model, B, device, den, xs, x0, eta=nz is not None)
+    step = _ddim_step(s, coef, True, nz)
 
     def loop():
-        if rs is not None:
-            rs.begin(xs)
-            for i in range(len(ts)):
-                rs.step(tt[i], 6, coef8[i], noise=nz.site(i))
-            x0.copy_(rs.image(rs.x0))
-            xs.copy_(rs.image(rs.x))
-            return
+        s.begin(xs)
         for i in range(len(ts)):
-            den.step_(xs, tt[i], 4, x0, coef4[i])
-            nz.add_(xs, i, sigma[i])
+            step(i, tt[i])
+        s.write_back(x=xs, x0=x0)
 
-    st = {"key": den.key(), "x": xs, "x0": x0, "noise": nz, "loop": _GraphLoop(loop, device)}
-    cache[key] = st
-    return st
+    return _LoopState(den.key(), xs, _GraphLoop(loop, device), x0, noise=nz)
 
 
 @torch.no_grad()
@@ -690,46 +686,15 @@ def ddim_from_starts(model, x: torch.Tensor, starts: Sequence[int], k: int, devi
     starts = [int(s) for s in starts]
     eta = float(eta)
     ddim_coefficients_eta(T, max(starts), k, eta)  # (ValueError for eta outside [0, 1])
-    if eta > 0:
-        st = _from_starts_eta(model, B, starts, k, device, eta)
-        st["x"].copy_(x.to(device).float())
-        st["noise"].set_seed(draw_noise_seed() if noise_seed is None else noise_seed)
-        st["loop"].run(use_graph and device.type == "cuda")
-        return st["x0"].clone()
     key = ("img2img", B, tuple(starts), k, str(device))
-    cache = _cache(model)
-    st = cache.pop(key, None)
-    if st is not None:
-        cache[key] = st  # most recently used last
-    if st is None or st["key"] != _Denoiser.key_of(model):
-        cached = [c for c in cache if isinstance(c, tuple) and c[0] == "img2img"]
-        for old in cached[:max(0, len(cached) - IMG2IMG_GRAPHS + 1)]:
-            del cache[old]
-        den = _Denoiser(model, device)
-        ts, coef = starts_table(T, starts, k)
-        coef = coef.to(device)
-        xs = torch.zeros(B, model.in_chans, *model.img_size, device=device)
-        x0 = torch.zeros_like(xs)
-        tt = torch.tensor(ts, dtype=torch.int64, device=device).unsqueeze(1).expand(-1, B).contiguous()
-        pbuf = _patch_rows(model, B, device, den)
-        rs = _rows_state(model, B, device, den)
-
-        def loop():
-            if rs is not None:
-                rs.begin(xs)
-                for i in range(len(ts)):
-                    rs.step(tt[i], 4, coef[i])
-                x0.copy_(rs.image(rs.x0))
-                xs.copy_(rs.image(rs.x))
-                return
-            for i in range(len(ts)):
-                den.step_(xs, tt[i], 4, x0, coef[i], patches=_chain_patches(pbuf, i == 0))
-
-        st = {"key": den.key(), "x": xs, "x0": x0, "loop": _GraphLoop(loop, device)}
-        cache[key] = st
-    st["x"].copy_(x.to(device).float())
-    st["loop"].run(use_graph and device.type == "cuda")
-    return st["x0"].clone()
+    if eta > 0:
+        key = ("img2img_eta", B, tuple(starts), k, str(device), eta)
+    st = _cached_loop(model, key, lambda: _from_starts_state(model, B, starts, k, device, eta), IMG2IMG_GRAPHS)
+    st.x.copy_(x.to(device).float())
+    if st.noise is not None:
+        st.noise.set_seed(draw_noise_seed() if noise_seed is None else noise_seed)
+    st.loop.run(use_graph and device.type == "cuda")
+    return st.x0.clone()
 
 
 @torch.no_grad()

@@ -261,6 +261,24 @@ class Saved:
     rf: Optional[torch.Tensor] = None
 
 
+@dataclass(frozen=True)
+class HeadStep:
+    """A sampler step fused into the head GEMM (``ops.head_step_`` / ``ops.head_step_rows_``):
+    ``img`` (the current x_t) is updated in place under ``mode`` (``ops.HEAD_*``) with the
+    device coefficient row(s) ``coef``; ``x0_out`` gets the clamped x0-hat.  LayerNorm-folded
+    program only: ``patches_in`` / ``patches_out`` hand the bf16 patch rows of x_t from one
+    step's head to the next step's embedding; with ``rows_w`` (the column-permuted embedding
+    weight, ``ops.embed_weight_rows``) the sampler state lives in patch rows; ``noise =
+    (rng, site)`` is the step's noise, drawn in the head epilogue (``HEAD_ETA`` / ``HEAD_ETA_EACH``)."""
+    mode: int
+    x0_out: Optional[torch.Tensor] = None
+    coef: Optional[torch.Tensor] = None
+    patches_in: Optional[torch.Tensor] = None
+    patches_out: Optional[torch.Tensor] = None
+    rows_w: Optional[torch.Tensor] = None
+    noise: Optional[tuple] = None
+
+
 class ViTProgram:
     def __init__(self, cfg: ProgramConfig):
         self.cfg = cfg
@@ -285,9 +303,8 @@ class ViTProgram:
     # ------------------------------------------------------------------ forward
     def forward(self, P: ModelTensors, img: torch.Tensor, t: torch.Tensor, rng: torch.Tensor, training: bool,
                 save: bool = True, head_step=None, loss=None, cold=None):
-        """``head_step = (mode, x0_out, coef)`` fuses the sampler update into the head
-        GEMM (``ops.head_step_``): ``img`` (the current x_t) is updated in place and
-        returned; mode 1 = DDIM step, mode 2 = clamp (cold sampler).  ``loss =
+        """``head_step`` (a :class:`HeadStep`) fuses the sampler update into the head
+        GEMM: ``img`` (the current x_t) is updated in place and returned.  ``loss =
         (target, beta)`` (LayerNorm-folded program only, see :meth:`supports_fused_loss`)
         returns ``(loss_parts, dtok)`` from :func:`ops.head_loss` instead of the image.
         ``cold`` (LayerNorm-folded program only): the cold batch draw fused into the
@@ -325,8 +342,8 @@ class ViTProgram:
             l1, m1, r1 = ln_n, m_n, r_n
         lf, mf, rf = l1, m1, r1
         if head_step is not None:
-            mode, x0_out, coef = head_step[:3]  # (patch-row hand-off: folded forward only)
-            ops.head_step_(lf, P.head_w, P.head_b, img, x0_out, coef, c.patch, mode)
+            hs = head_step  # (its patch-row hand-off: folded forward only)
+            ops.head_step_(lf, P.head_w, P.head_b, img, hs.x0_out, hs.coef, c.patch, hs.mode)
             return img, S
         out = ops.head_fwd(lf, P.head_w, P.head_b, B, c.chans, c.img_h, c.img_w, c.patch)
         if save:
@@ -353,14 +370,13 @@ class ViTProgram:
         # each slot written once by the producing epilogue
         st = torch.empty(2 * L + 1, M, D // 32, 2, dtype=torch.float32, device=dev)
         xb = torch.empty(M, D, dtype=ACT_DTYPE, device=dev)
-        # sampler steps: head_step = (mode, x0_out, coef, patches_in, patches_out[,
-        # pe_w_rows[, noise]]); the previous step's head left this step's bf16 patch rows in
-        # patches_in.  With pe_w_rows the sampler state lives in patch rows
+        # sampler steps (HeadStep): the previous step's head left this step's bf16 patch
+        # rows in patches_in.  With rows_w the sampler state lives in patch rows
         # (ops.image_to_rows; ``img`` is a [B, C, H, W]-shaped view of that buffer):
         # the embedding reads the rows through the column-permuted weight and the
         # head updates them with contiguous vector accesses (ops.head_step_rows_)
-        patches_in = head_step[3] if head_step is not None and len(head_step) > 3 else None
-        rows_w = head_step[5] if head_step is not None and len(head_step) > 5 else None
+        hs = head_step
+        patches_in, rows_w = (hs.patches_in, hs.rows_w) if hs is not None else (None, None)
         if rows_w is not None and patches_in is None:
             raise ValueError("the patch-row sampler state needs patches_in")
         # the fused batch draw writes the loss target as patch rows for the vector
@@ -404,20 +420,17 @@ class ViTProgram:
                 # the LayerNorm backwards read the bf16 copies the folded GEMMs normalised
                 xs0, xs1 = (x0b, x1b) if LN_BWD_XB else (x0, x1)
                 S.blocks.append((xs0, None, m1, r1, qkv, o, lse, xs1, None, m2, r2, u, h))
-        if head_step is not None:
-            mode, x0_out, coef = head_step[:3]
-            patches_out = head_step[4] if len(head_step) > 4 else None
-            noise = head_step[6] if len(head_step) > 6 else None  # modes 5 / 6: (rng, site) of the step's noise
+        if hs is not None:
             if rows_w is not None:
                 F = P.head_wf.shape[0]
                 ops.head_step_rows_(xb, P.head_wf, P.head_bf, img.view(-1, F),
-                                    None if x0_out is None else x0_out.view(-1, F), coef, B, mode,
-                                    patches_out=patches_out, fold=(st[2 * L], P.head_c, c.eps), noise=noise)
+                                    None if hs.x0_out is None else hs.x0_out.view(-1, F), hs.coef, B, hs.mode,
+                                    patches_out=hs.patches_out, fold=(st[2 * L], P.head_c, c.eps), noise=hs.noise)
                 return img, S
-            if noise is not None:
+            if hs.noise is not None:
                 raise ValueError("head modes 5 / 6 (noise in the head epilogue) need the patch-row sampler state")
-            ops.head_step_(xb, P.head_wf, P.head_bf, img, x0_out, coef, c.patch, mode, patches_out=patches_out,
-                           fold=(st[2 * L], P.head_c, c.eps))
+            ops.head_step_(xb, P.head_wf, P.head_bf, img, hs.x0_out, hs.coef, c.patch, hs.mode,
+                           patches_out=hs.patches_out, fold=(st[2 * L], P.head_c, c.eps))
             return img, S
         mf, rf = stats()
         if loss is not None:  # training: the loss and its token-layout gradient from the head GEMM

@@ -24,6 +24,7 @@ __all__ = [
     "sqnorm", "adamw_step", "weight_ema_decay", "advance_counters", "ddim_step", "ddim_step_", "randn_", "q_sample",
     "pixelate_pair", "cold_batch", "gauss_batch", "head_step_rows_", "cold_step_", "cold_step_rows_",
     "image_to_rows", "rows_to_image", "embed_weight_rows", "patch_embed_cold_fwd", "ln_fold_", "SITE_STEP_NOISE",
+    "HEAD_DDIM", "HEAD_CLAMP", "HEAD_DDIM_EACH", "HEAD_ETA", "HEAD_ETA_EACH",
 ]
 
 
@@ -199,7 +200,7 @@ def head_step_(a, w, b, x, x0_out, coef, patch: int, mode: int, fold=None, patch
         return _ops().head_step_(a, w, b, x, x0_out, coef, patch, mode, st, c, eps, patches_out)
     B, C, H, W = x.shape
     x0_raw = ref.head_fwd(a, w, b, B, C, H, W, patch, st, c, eps)
-    if mode == 2:
+    if mode == HEAD_CLAMP:
         x.copy_(torch.clamp(x0_raw, -1.0, 1.0))
     else:
         xn, x0 = ref.ddim_step(x, x0_raw, _ddim_coef(coef, x))
@@ -234,6 +235,10 @@ def embed_weight_rows(w_pe, C: int, patch: int):
 # noise site of sampling step i (0-based from the top of the grid): SITE_STEP_NOISE + i, clear
 # of the model's sites (1, 16 + 8 block + 0..5) and the data sites (3, 4)
 SITE_STEP_NOISE = 4096
+# head-step modes (the values csrc/bindings.cpp and csrc/gemm_epi.h test): clamp + DDIM update
+# with one coefficient row / clamp only / DDIM with one row per sample / the stochastic
+# (eta > 0) DDIM step with one row of 8 / with one row of 8 per sample
+HEAD_DDIM, HEAD_CLAMP, HEAD_DDIM_EACH, HEAD_ETA, HEAD_ETA_EACH = 1, 2, 4, 5, 6
 
 
 def head_step_rows_(a, w, b, x, x0_out, coef, batch: int, mode: int, fold=None, patches_out=None, noise=None):
@@ -248,7 +253,7 @@ def head_step_rows_(a, w, b, x, x0_out, coef, batch: int, mode: int, fold=None, 
     column) of ``randn_(buf like x, rng, site)``, drawn inside the head epilogue on a GPU (no
     noise buffer, no extra launch); ``rng`` a device int64[2] ``{seed, 0}``."""
     st, c, eps, _, _ = _fold_args(fold)
-    noisy = int(mode) in (5, 6)
+    noisy = int(mode) in (HEAD_ETA, HEAD_ETA_EACH)
     if noisy != (noise is not None):
         raise ValueError("head_step_rows_: modes 5 / 6 take noise=(rng, site), the other modes take none")
     if _hip(a):
@@ -261,21 +266,22 @@ def head_step_rows_(a, w, b, x, x0_out, coef, batch: int, mode: int, fold=None, 
     y = ref._lin(a, w, b, st, c, eps)
     y = y.reshape(batch, NP + 1, F)[:, 1:].reshape(batch * NP, F)
     x0 = torch.clamp(y, -1.0, 1.0)
-    if mode == 2:
+    if mode == HEAD_CLAMP:
         x.copy_(x0)
     elif noisy:
-        if coef.numel() != (8 * batch if mode == 6 else 8):
+        if coef.numel() != (8 * batch if mode == HEAD_ETA_EACH else 8):
             raise ValueError("head_step_rows_: modes 5 / 6 take coefficient rows of 8 floats")
         z = torch.empty_like(x)
         randn_(z, noise[0], int(noise[1]))
         cf = coef.reshape(-1, 8).float()
-        cf = cf.repeat_interleave(NP, 0) if mode == 6 else cf.expand(x.shape[0], 8)
+        cf = cf.repeat_interleave(NP, 0) if mode == HEAD_ETA_EACH else cf.expand(x.shape[0], 8)
         xn, _ = ref.ddim_step_eta(x, y, cf, z)
         x.copy_(xn)
         x0_out.copy_(x0)
     else:
         cf = coef.reshape(-1, 4).float()
-        cf = cf.repeat_interleave(NP, 0) if cf.shape[0] == batch and mode == 4 else cf[:1].expand(x.shape[0], 4)
+        each = cf.shape[0] == batch and mode == HEAD_DDIM_EACH
+        cf = cf.repeat_interleave(NP, 0) if each else cf[:1].expand(x.shape[0], 4)
         eps_hat = (x - cf[:, 0:1] * x0) / cf[:, 1:2]
         x.copy_(cf[:, 2:3] * x0 + cf[:, 3:4] * eps_hat)
         x0_out.copy_(x0)

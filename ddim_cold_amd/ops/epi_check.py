@@ -604,12 +604,12 @@ def run_ddim(device, geom) -> float:
     a, w, bias, raw, x_t = (t.to(device) for t in (c.a, c.w, c.bias, c.raw, c.x_t))
     tag = f"B={B} C={C} {H}x{W} p={p}"
     worst = 0.0
-    runs = [(1, (t,)) for t in DDIM_TS] + [(4, ts) for ts in DDIM_MODE4]
+    runs = [(ops.HEAD_DDIM, (t,)) for t in DDIM_TS] + [(ops.HEAD_DDIM_EACH, ts) for ts in DDIM_MODE4]
     for mode, ts in runs:
         rows = ddim_rows(ts)
-        coef = (rows[0] if mode == 1 else rows).contiguous().to(device)
+        coef = (rows[0] if mode == ops.HEAD_DDIM else rows).contiguous().to(device)
         nm = f"mode {mode} t={ts} {tag}"
-        if mode == 1:
+        if mode == ops.HEAD_DDIM:
             xn, x0 = ops.ddim_step(x_t, raw, coef)
             worst = max(worst, check_ddim(xn, x0, c, rows, ts, "ddim_step " + nm))
         x, x0o = x_t.clone(), torch.full_like(x_t, float("nan"))

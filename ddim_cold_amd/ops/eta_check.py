@@ -113,7 +113,7 @@ def ops_step(case: DdimCase, device, x_t, coef, mode: int, rng=None, site: int =
     x = x_t.to(device).clone()
     x0 = torch.full((B * NP, F), float("nan"), device=device)
     po = torch.full((B * NP, F), float("nan"), dtype=torch.bfloat16, device=device)
-    noise = (rng.to(device), site) if mode in (5, 6) else None
+    noise = (rng.to(device), site) if mode in (ops.HEAD_ETA, ops.HEAD_ETA_EACH) else None
     ops.head_step_rows_(a, w, bias, x, x0, coef.contiguous().to(device), B, mode, patches_out=po, noise=noise)
     return x, x0, po
 
@@ -137,16 +137,16 @@ def ddim_eta_f32(case: DdimCase, device, x_t, coef, mode: int, rng=None, site: i
     x_t = x_t.detach().float().cpu()
     raw = case.bias.unsqueeze(0).expand(B * NP, F)
     x0 = raw.clamp(-1.0, 1.0)
-    if mode in (1, 4):
+    if mode in (ops.HEAD_DDIM, ops.HEAD_DDIM_EACH):
         cf = coef.detach().float().cpu().reshape(-1, 4)
-        cf = cf.repeat_interleave(NP, 0) if mode == 4 else cf.expand(B * NP, 4)
+        cf = cf.repeat_interleave(NP, 0) if mode == ops.HEAD_DDIM_EACH else cf.expand(B * NP, 4)
         c0, c1, c2, cd = (cf[:, i:i + 1] for i in range(4))
         xn = c2 * x0 + cd * ((x_t - c0 * x0) / c1)
         return xn, x0.clone(), xn.to(torch.bfloat16)
     cf = coef.detach().float().cpu().reshape(-1, 8)
-    if mode == 6 and mutant == "neighbour_sigma":
+    if mode == ops.HEAD_ETA_EACH and mutant == "neighbour_sigma":
         cf = torch.cat((cf[:, :4], cf.roll(-1, 0)[:, 4:]), 1)
-    cf = cf.repeat_interleave(NP, 0) if mode == 6 else cf.expand(B * NP, 8)
+    cf = cf.repeat_interleave(NP, 0) if mode == ops.HEAD_ETA_EACH else cf.expand(B * NP, 8)
     c0, c1, c2, cd, sg = (cf[:, i:i + 1] for i in range(5))
     z = torch.empty(B * NP, F)
     if mutant == "column_noise":
@@ -175,7 +175,7 @@ def mutant_step(mutant: str) -> Callable:
 def probe_noise(case: DdimCase, device, rng, site: int, step: Callable = ops_step) -> torch.Tensor:
     """The implementation's own ``z`` [B*P, F] (on ``device``) at (rng, site): mode 5 with the probe row."""
     x_t, _ = case_rows(case)
-    x, _, _ = step(case, device, x_t, torch.tensor(PROBE_ROW), 5, rng, site)
+    x, _, _ = step(case, device, x_t, torch.tensor(PROBE_ROW), _ops().HEAD_ETA, rng, site)
     return x
 
 
@@ -238,13 +238,13 @@ def run_eta(device, geom, step: Callable = ops_step) -> float:
         for n, t in enumerate(ETA_TS):
             i = STEPS[n % len(STEPS)]
             rows = eta_rows((t,), eta)
-            x, x0, po = step(case, device, x_t, rows[0], 5, rng, step_site(i))
+            x, x0, po = step(case, device, x_t, rows[0], _ops().HEAD_ETA, rng, step_site(i))
             worst = max(worst, check_eta(x, x0, po, case, rows, zs[i], (t,), f"mode 5 eta={eta} t={t} {geom}"))
         for n, shift in enumerate(MODE6_SHIFTS):
             i = STEPS[n % len(STEPS)]
             ts = mode6_ts(B, shift)
             rows = eta_rows(ts, eta)
-            x, x0, po = step(case, device, x_t, rows, 6, rng, step_site(i))
+            x, x0, po = step(case, device, x_t, rows, _ops().HEAD_ETA_EACH, rng, step_site(i))
             worst = max(worst, check_eta(x, x0, po, case, rows, zs[i], ts, f"mode 6 eta={eta} t={ts} {geom}"))
     return worst
 
@@ -253,7 +253,7 @@ def run_eta(device, geom, step: Callable = ops_step) -> float:
 def run_exact(device, geom, step: Callable = ops_step) -> None:
     """sigma = 0 rows against modes 1 / 4 on the same inputs (x, x0_out, patches_out to the bit),
     and the identity row of mode 6 (x stays x_t to the bit)."""
-    case = ddim_case(geom)
+    ops, case = _ops(), ddim_case(geom)
     B, NP, F = dims(geom)
     x_t, _ = case_rows(case)
     rng = rng_of(device)
@@ -261,18 +261,18 @@ def run_exact(device, geom, step: Callable = ops_step) -> None:
     for t in ETA_TS:
         rows8, rows4 = eta_rows((t,), 0.0), ddim_rows((t,))
         assert torch.equal(rows8[:, :4], rows4) and float(rows8[0, 4]) == 0.0
-        got = step(case, device, x_t, rows8[0], 5, rng, site)
-        want = step(case, device, x_t, rows4[0], 1)
+        got = step(case, device, x_t, rows8[0], ops.HEAD_ETA, rng, site)
+        want = step(case, device, x_t, rows4[0], ops.HEAD_DDIM)
         for g, w_, nm in zip(got, want, ("x", "x0_out", "patches_out")):
             assert_exact(g, w_, f"mode 5 with sigma = 0 against mode 1, t={t} {geom}: {nm}")
     for shift in MODE6_SHIFTS:
         ts = mode6_ts(B, shift)
         rows8, rows4 = eta_rows(ts, 0.0), ddim_rows(ts)
-        got = step(case, device, x_t, rows8, 6, rng, site)
-        want = step(case, device, x_t, rows4, 4)
+        got = step(case, device, x_t, rows8, ops.HEAD_ETA_EACH, rng, site)
+        want = step(case, device, x_t, rows4, ops.HEAD_DDIM_EACH)
         for g, w_, nm in zip(got, want, ("x", "x0_out", "patches_out")):
             assert_exact(g, w_, f"mode 6 with sigma = 0 against mode 4, t={ts} {geom}: {nm}")
-    x, _, _ = step(case, device, x_t, eta_rows((None,) * B, 1.0), 6, rng, site)
+    x, _, _ = step(case, device, x_t, eta_rows((None,) * B, 1.0), ops.HEAD_ETA_EACH, rng, site)
     assert_exact(x, x_t, f"mode 6 identity rows {geom}: x against x_t")
 
 

@@ -186,7 +186,7 @@ def test_restore_mixed_levels(model):
     assert (out[3] - start[3].clamp(-1, 1)).abs().mean() > 0.25  # the loop did something
     cache = model.__dict__["_sampler_graphs"]
     keys = lambda: [k for k in cache if k[0] == "cold_restore"]  # noqa: E731
-    first = cache[keys()[0]]["loop"]
+    first = cache[keys()[0]].loop
     assert torch.equal(s.restore(imgs, levels, unit=False), out) and first.replays == 1
     # another level tuple: a graph of its own; the first one still replays to the same result
     other = s.restore(imgs, [6, 3, 1, 0], unit=False)

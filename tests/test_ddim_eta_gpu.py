@@ -173,11 +173,11 @@ def test_eta_sampler_matches_eager_reference(model):
     print(f"eta=1 k=400 N=8: mean |d| {d.mean():.4f} max |d| {d.max():.4f}")
     assert d.mean() < 0.01 and d.max() < 0.2, (d.mean(), d.max())
     st = s._state(8, False)
-    assert st["loop"].graph is not None and st["loop"].replays == 0
+    assert st.loop.graph is not None and st.loop.replays == 0
     out2 = smp.DDIMSampler(model, DEV, k=400, eta=1.0).sample(8, noise=noise, noise_seed=SEED)
-    assert st["loop"].replays == 1 and torch.equal(out, out2)        # a replay reproduces the capture run
+    assert st.loop.replays == 1 and torch.equal(out, out2)        # a replay reproduces the capture run
     other = s.sample(8, noise=noise, noise_seed=SEED + 1)            # a new seed needs no new capture
-    assert st["loop"].replays == 2 and not torch.equal(other, out)
+    assert st.loop.replays == 2 and not torch.equal(other, out)
     seq = s.sequence(8, noise=noise, noise_seed=SEED)
     assert len(seq) == 6 and torch.equal(seq[-1], out)
     det = smp.DDIMSampler(model, DEV, k=400).sample(8, noise=noise)

@@ -255,7 +255,7 @@ def test_scope_sampler_graph_replays_on_swapped_weights():
     smp = DDIMSampler(model, DEV, k=500)  # 4 steps
     twin = _ema_twin(eng)
     first = smp.sample(2, noise=noise)
-    loop = next(iter(_cache(model).values()))["loop"]
+    loop = next(iter(_cache(model).values())).loop
     assert loop.graph is not None
     with eng.ema_weights():
         mid = smp.sample(2, noise=noise)

@@ -26,7 +26,7 @@ for s in samplers.values():  # capture, then warm the replay
 res = {k: ([], []) for k in variants}
 for r in range(rounds):
     for name, s in samplers.items():
-        loop = s._state(N)["loop"]
+        loop = s._state(N).loop
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         torch.cuda.synchronize()
         e0.record()

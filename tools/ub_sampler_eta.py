@@ -32,7 +32,7 @@ for name, (eta, rows) in variants.items():  # build each loop under its ROWS set
     s = smp.DDIMSampler(model, "cuda", k=K, eta=eta)
     for _ in range(3):
         s.sample(N, generator=torch.Generator().manual_seed(0))
-    loops[name] = (s, s._state(N, False)["loop"])
+    loops[name] = (s, s._state(N, False).loop)
     smp.ROWS = True
 steps = len(loops["eta=0"][0].ts)
 res = {k: [] for k in variants}
