@@ -23,7 +23,7 @@ from __future__ import annotations
 import math
 import os
 from dataclasses import dataclass, field
-from typing import Callable, Dict, Iterator, List, Optional
+from typing import Callable, Dict, FrozenSet, Iterator, List, NamedTuple, Optional
 
 import torch
 
@@ -249,12 +249,33 @@ class ProgramConfig:
         return self.chans * self.patch * self.patch
 
 
+class BlockSaved(NamedTuple):
+    """What one block's forward saves for its backward: the inputs of norm1 / norm2
+    (``x0`` / ``x1``; the folded forward saves their bf16 copies under ``LN_BWD_XB``), the
+    LayerNorm outputs ``l1`` / ``l2`` (None when folded: the backward re-emits them) with
+    their row statistics, the attention operands, fc1's pre-activation ``u`` and output
+    ``h``, and the stored attention-dropout keep flags (None: the backward re-hashes)."""
+    x0: torch.Tensor
+    l1: Optional[torch.Tensor]
+    m1: torch.Tensor
+    r1: torch.Tensor
+    qkv: torch.Tensor
+    o: torch.Tensor
+    lse: torch.Tensor
+    x1: torch.Tensor
+    l2: Optional[torch.Tensor]
+    m2: torch.Tensor
+    r2: torch.Tensor
+    u: torch.Tensor
+    h: torch.Tensor
+    keep: Optional[torch.Tensor] = None
+
+
 @dataclass
 class Saved:
     t: torch.Tensor
     patches: torch.Tensor
-    blocks: list = field(default_factory=list)
-    keeps: list = field(default_factory=list)  # per block: stored attention keep flags or None
+    blocks: List[BlockSaved] = field(default_factory=list)
     xL: Optional[torch.Tensor] = None
     lf: Optional[torch.Tensor] = None
     mf: Optional[torch.Tensor] = None
@@ -277,6 +298,50 @@ class HeadStep:
     patches_out: Optional[torch.Tensor] = None
     rows_w: Optional[torch.Tensor] = None
     noise: Optional[tuple] = None
+
+
+@dataclass(frozen=True)
+class BackwardPlan:
+    """How :meth:`ViTProgram.backward_iter` schedules the deferred weight gradients and the
+    LayerNorm / embedding gradient finalizes (default: one launch after the backward).
+
+    ``ln_ws`` ([2L+1, R, 2D], zero) collects the LayerNorm dgamma/dbeta replicas in
+    backward order (final norm, then norm2 / norm1 of blocks L-1..0); the caller
+    finalises them with ``ops.replica_reduce_``, or ``ln_final`` (``ops.LnFinal``) does in
+    the embedding-backward launch.  ``embed_with_block0``: the embedding backward runs
+    before block 0's weight gradients are flushed (no separate embedding bucket).
+    ``flush_at`` (block indices; data parallel): one weight-gradient launch per gradient
+    bucket -- after each listed block and after the embedding backward -- so the bucket's
+    all-reduce can start while the rest of the backward runs.  ``store``: the block / head
+    weight-gradient targets have no other writer this step, so the deferred launches write
+    instead of read-add-writing them (the embedding bucket's patch gradient still adds).
+    ``grad_norm`` (``ops.GradNorm``; one deferred launch, no ``flush_at``): that launch
+    also writes the grad-norm partials of the whole gradient arena, so the optimizer needs
+    no sqnorm pass.  ``owners`` (>= the distinct timesteps of a batch; with ``grad_norm``
+    and ``embed_with_block0``): no embedding-backward launch -- the last LayerNorm backward
+    writes the patch-row gradient, and the cls / pos / time-embedding gradients and
+    ``ln_final`` (with its ``offs``) run as extra workgroups of the weight-gradient launch.
+    ``tickets``: the caller's ``ops.wgrad_tickets`` buffer for the deferred launches (a
+    captured backward over >= 16,384 tokens needs one)."""
+    ln_ws: Optional[torch.Tensor] = None
+    embed_with_block0: bool = False
+    ln_final: Optional[ops.LnFinal] = None
+    flush_at: Optional[FrozenSet[int]] = None
+    store: bool = False
+    grad_norm: Optional[ops.GradNorm] = None
+    owners: Optional[int] = None
+    tickets: Optional[torch.Tensor] = None
+
+    def __post_init__(self):
+        if self.grad_norm is not None and self.flush_at is not None:
+            raise ValueError("grad_norm needs the single deferred weight-gradient launch (no flush_at)")
+        if self.owners is not None and (self.grad_norm is None or not self.embed_with_block0):
+            raise ValueError("owners (embedding gradients in the weight-gradient launch) needs grad_norm and "
+                             "embed_with_block0")
+        if self.ln_final is not None and self.ln_ws is None:
+            raise ValueError("ln_final finalises ln_ws: it needs the workspace")
+        if self.owners is not None and self.ln_final is not None and self.ln_final.offs is None:
+            raise ValueError("ln_final in the weight-gradient launch needs LnFinal.offs")
 
 
 class ViTProgram:
@@ -338,7 +403,7 @@ class ViTProgram:
             x = ops.linear_residual_fwd(h, bp.fc2_w, bp.fc2_b, x1, N, rng, sf2, pd, sd2, dpr[i])
             ln_n, m_n, r_n = ops.layernorm_fwd(x, nw, nb, c.eps)
             if save:
-                S.blocks.append((x0, l1, m1, r1, qkv, o, lse, x1, l2, m2, r2, u, h))
+                S.blocks.append(BlockSaved(x0, l1, m1, r1, qkv, o, lse, x1, l2, m2, r2, u, h))
             l1, m1, r1 = ln_n, m_n, r_n
         lf, mf, rf = l1, m1, r1
         if head_step is not None:
@@ -404,8 +469,6 @@ class ViTProgram:
             qkv = ops.qkv_fwd(xb, bp.qkv_wf, bp.qkv_bf, B, N, c.heads, fold=fold)
             keep = ops.attn_keep_buffer(qkv, ad) if save and STORE_ATTN_KEEP else None
             o, lse = ops.attn_fwd(qkv, c.scale, rng, sa, ad, keep_out=keep)
-            if save:
-                S.keeps.append(keep)
             o = o.view(M, D)
             x1b = torch.empty(M, D, dtype=ACT_DTYPE, device=dev)
             x1 = ops.linear_residual_fwd(o, bp.proj_w, bp.proj_b, x0, N, rng, sp, pd, sd1, dpr[i],
@@ -419,7 +482,7 @@ class ViTProgram:
             if save:
                 # the LayerNorm backwards read the bf16 copies the folded GEMMs normalised
                 xs0, xs1 = (x0b, x1b) if LN_BWD_XB else (x0, x1)
-                S.blocks.append((xs0, None, m1, r1, qkv, o, lse, xs1, None, m2, r2, u, h))
+                S.blocks.append(BlockSaved(xs0, None, m1, r1, qkv, o, lse, xs1, None, m2, r2, u, h, keep))
         if hs is not None:
             if rows_w is not None:
                 F = P.head_wf.shape[0]
@@ -450,9 +513,7 @@ class ViTProgram:
     # ------------------------------------------------------------------ backward
     def backward_iter(self, P: ModelTensors, G: ModelTensors, S: Saved, dtok: torch.Tensor, rng: torch.Tensor,
                       training: bool = True, wgrad: Optional[Callable] = None,
-                      ln_ws: Optional[torch.Tensor] = None, embed_with_block0: bool = False, ln_final=None,
-                      wgrad_flush=None, wgrad_store: bool = False, wgrad_sq=None,
-                      embed_fused=None, wgrad_tickets=None) -> Iterator[int]:
+                      plan: BackwardPlan = BackwardPlan()) -> Iterator[int]:
         """Hand-written backward; yields the block index after each block's input
         gradients are issued (L-1 first, then ..., 0) and -1 after the embedding grads.
 
@@ -460,41 +521,23 @@ class ViTProgram:
         by default EVERY ``dW += dy^T x`` of the backward (4 per block, head, patch
         embedding) is queued and issued as ONE launch after the embedding backward
         (:func:`ops.linear_wgrad_multi`; nothing reads a block's gradients before the
-        optimizer), so a block yield only marks the order.  ``wgrad_flush`` (a set of
-        block indices; data parallel): one such launch per gradient bucket -- after
-        each listed block and after the embedding backward -- so the bucket's
-        all-reduce can start while the rest of the backward runs.  A ``wgrad``
-        callable instead receives each job as soon as its operands exist.
-        ``ln_ws`` ([2L+1, R, 2D], zero) collects LayerNorm dgamma/dbeta replicas in
-        backward order (final norm, then norm2/norm1 of blocks L-1..0); the caller
-        finalises them with ``ops.replica_reduce_`` (or ``ln_final``, carried by the
-        embedding-backward launch).  ``embed_with_block0``: the embedding backward
-        runs before block 0's weight gradients are flushed (no separate embedding
-        bucket).  ``wgrad_store``: the block / head weight-gradient targets have no
-        other writer this step, so the deferred launches write instead of
-        read-add-writing them (the embedding bucket's patch gradient still adds).
-        ``wgrad_sq = (parts, arena, lazy)`` (one deferred launch, no ``wgrad_flush``):
-        that launch also writes the grad-norm partials of the whole gradient arena
-        (:func:`ops.linear_wgrad_multi`), so the optimizer needs no sqnorm pass.
-        ``embed_fused = (owners, ln_offs)`` (with ``wgrad_sq``): no embedding-backward
-        launch -- the last LayerNorm backward writes the patch-row gradient and the
-        cls / pos / time-embedding gradients and the LayerNorm finalize (``ln_final``,
-        ``ln_offs`` = its destinations' arena offsets) run as extra workgroups of the
-        weight-gradient launch (``owners`` >= the distinct timesteps of a batch).
-        ``wgrad_tickets``: the caller's :func:`ops.wgrad_tickets` buffer for the deferred
-        launches (a captured backward over >= 16,384 tokens needs one).
+        optimizer), so a block yield only marks the order; ``plan`` (a
+        :class:`BackwardPlan`) schedules them otherwise.  A ``wgrad`` callable instead
+        receives each job as soon as its operands exist.
         Measured slower on MI355X and removed: weight gradients riding in the
         input-gradient launches, one grouped launch per block, a side-stream branch
         for them, the proj input gradient inside the attention backward, the
         LayerNorm backward in the epilogue or the prologue of its neighbouring GEMM
         (profiles/fused_ln_qkv_r5_ab.txt, profiles/ln_prologue_r5.md)."""
+        ln_ws, merge, ln_final = plan.ln_ws, plan.embed_with_block0, plan.ln_final
+
         def ws(k):
             return None if ln_ws is None else ln_ws[k]
-        bucketed = wgrad is None and wgrad_flush is not None
-        if wgrad_sq is not None and (bucketed or wgrad is not None):
-            raise ValueError("wgrad_sq needs the single deferred weight-gradient launch")
-        if embed_fused is not None and (wgrad_sq is None or G.temb is None or not embed_with_block0):
-            raise ValueError("embed_fused needs wgrad_sq, a trainable time embedding and embed_with_block0")
+        bucketed = wgrad is None and plan.flush_at is not None
+        if plan.grad_norm is not None and wgrad is not None:
+            raise ValueError("grad_norm needs the single deferred weight-gradient launch")
+        if plan.owners is not None and G.temb is None:
+            raise ValueError("the embedding gradients in the weight-gradient launch need a trainable time embedding")
         emb_spec = None
         jobs = []
         if wgrad is None:
@@ -535,55 +578,49 @@ class ViTProgram:
                          dpr[L - 1], True, ws(0), beta=P.nb if fold else None, y_out=lf if fold else None)
         wgrad(dtok, lf, G.head_w, G.head_b)
         for i in range(L - 1, -1, -1):
-            x0, l1, m1, r1, qkv, o, lse, x1, l2, m2, r2, u, h = S.blocks[i]
+            sv = S.blocks[i]
             bp, bg = P.blocks[i], G.blocks[i]
             sa, sp, sd1, sf1, _, _ = block_sites(i)
-            du = ops.linear_dgrad_gelu(gy, bp.fc2_w, u, rng, sf1, pd, wt=bp.fc2_wt)
-            wgrad(gy, h, bg.fc2_w, bg.fc2_b)
+            du = ops.linear_dgrad_gelu(gy, bp.fc2_w, sv.u, rng, sf1, pd, wt=bp.fc2_wt)
+            wgrad(gy, sv.h, bg.fc2_w, bg.fc2_b)
             k2 = 1 + 2 * (L - 1 - i)
-            l2 = ln_out(l2)
-            g1, gy1 = dgrad_ln(du, bp.fc1_w, 1, x1, m2, r2, bp.n2w, g, bg.n2w, bg.n2b, N, rng, sp, pd, sd1,
+            l2 = ln_out(sv.l2)
+            g1, gy1 = dgrad_ln(du, bp.fc1_w, 1, sv.x1, sv.m2, sv.r2, bp.n2w, g, bg.n2w, bg.n2b, N, rng, sp, pd, sd1,
                                dpr[i], True, ws(k2), beta=bp.n2b if fold else None, y_out=l2 if fold else None,
                                wt=bp.fc1_wt)
             do = dgrad(gy1, bp.proj_w, bp.proj_wt, False)
             wgrad(du, l2, bg.fc1_w, bg.fc1_b)
-            wgrad(gy1, o, bg.proj_w, bg.proj_b)
-            dqkv = ops.attn_bwd(do, qkv, o, lse, c.scale, rng, sa, ad,
-                                keep=S.keeps[i] if len(S.keeps) == L else None)
+            wgrad(gy1, sv.o, bg.proj_w, bg.proj_b)
+            dqkv = ops.attn_bwd(do, sv.qkv, sv.o, sv.lse, c.scale, rng, sa, ad, keep=sv.keep)
             qs = QKV_DGRAD_SPLITS if 3 * D >= 768 else 1
-            l1 = ln_out(l1)
+            l1 = ln_out(sv.l1)
             fk = dict(beta=bp.n1b, y_out=l1) if fold else {}
             if i > 0:
                 _, _, _, _, psf2, psd2 = block_sites(i - 1)
-                g, gy = dgrad_ln(dqkv, bp.qkv_w, qs, x0, m1, r1, bp.n1w, g1, bg.n1w, bg.n1b, N, rng, psf2, pd, psd2,
-                                 dpr[i - 1], True, ws(k2 + 1), wt=bp.qkv_wt, **fk)
+                g, gy = dgrad_ln(dqkv, bp.qkv_w, qs, sv.x0, sv.m1, sv.r1, bp.n1w, g1, bg.n1w, bg.n1b, N, rng, psf2,
+                                 pd, psd2, dpr[i - 1], True, ws(k2 + 1), wt=bp.qkv_wt, **fk)
             else:
-                if embed_fused is not None:  # the patch-row gradient from this LayerNorm backward
+                if plan.owners is not None:  # the patch-row gradient from this LayerNorm backward
                     Bs = S.t.shape[0]
                     gpatch = torch.empty(Bs * (N - 1), D, dtype=ACT_DTYPE, device=dtok.device)
                     fk = dict(fk, gp_out=gpatch, site_emb=SITE_EMBED, p_emb=pd)
-                g, gy = dgrad_ln(dqkv, bp.qkv_w, qs, x0, m1, r1, bp.n1w, g1, bg.n1w, bg.n1b, N, rng, 0, 0.0, 0, 0.0,
-                                 False, ws(k2 + 1), wt=bp.qkv_wt, **fk)
+                g, gy = dgrad_ln(dqkv, bp.qkv_w, qs, sv.x0, sv.m1, sv.r1, bp.n1w, g1, bg.n1w, bg.n1b, N, rng, 0, 0.0,
+                                 0, 0.0, False, ws(k2 + 1), wt=bp.qkv_wt, **fk)
             keep.append((gy1, du, dqkv, l1, l2, do))
             wgrad(dqkv, l1, bg.qkv_w, bg.qkv_b)
-            if i == 0 and embed_with_block0 and embed_fused is not None:
+            if i == 0 and merge and plan.owners is not None:
                 wgrad(gpatch, S.patches, G.pe_w, G.pe_b)
-                owners, ln_offs = embed_fused
-                ln = None
-                if ln_final is not None:
-                    lw, lp, lC, lR = ln_final[:4]
-                    ln = (lw, lp, ln_offs, lC, lR, bool(ln_final[4]) if len(ln_final) > 4 else False)
-                emb_spec = (g.view(S.t.shape[0], N, D), S.t, rng, SITE_EMBED, pd, G.cls, G.pos, G.temb,
-                            min(int(owners), S.t.shape[0]), ln)
-            elif i == 0 and embed_with_block0:
+                emb_spec = ops.EmbedGrads(g.view(S.t.shape[0], N, D), S.t, rng, SITE_EMBED, pd, G.cls, G.pos, G.temb,
+                                          min(int(plan.owners), S.t.shape[0]), ln_final)
+            elif i == 0 and merge:
                 gpatch = self._embed_backward(P, G, S, g, rng, pd, wgrad, ln_final)
-            if bucketed and (i in wgrad_flush or (i == 0 and embed_with_block0)) and jobs:
+            if bucketed and (i in plan.flush_at or (i == 0 and merge)) and jobs:
                 # this bucket's weight gradients: final now
-                ops.linear_wgrad_multi(jobs, store=wgrad_store, tickets=wgrad_tickets)
+                ops.linear_wgrad_multi(jobs, store=plan.store, tickets=plan.tickets)
                 keep.append(jobs)
                 jobs = []
             yield i
-        if not embed_with_block0:
+        if not merge:
             gpatch = self._embed_backward(P, G, S, g, rng, pd, wgrad, ln_final)
         if jobs:
             tiles = sum(-(-dy.shape[1] // 64) * -(-x.shape[1] // 64) for dy, x, _, _ in jobs)
@@ -594,8 +631,8 @@ class ViTProgram:
                 for job in jobs:
                     ops.linear_wgrad(*job)
             else:
-                ops.linear_wgrad_multi(jobs, store=wgrad_store and not bucketed, sq=wgrad_sq, embed=emb_spec,
-                                       tickets=wgrad_tickets)
+                ops.linear_wgrad_multi(jobs, store=plan.store and not bucketed, sq=plan.grad_norm, embed=emb_spec,
+                                       tickets=plan.tickets)
             keep.append(jobs)
         keep.append((gpatch, lf))
         self._keep = keep  # operands of the queued launches stay referenced until the next step

@@ -9,7 +9,7 @@ PyTorch.
 from __future__ import annotations
 
 import math
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -402,24 +402,67 @@ def wgrad_tickets(device) -> torch.Tensor:
     return torch.zeros(WGRAD_TICKETS, dtype=torch.int32, device=device)
 
 
+class GradNorm(NamedTuple):
+    """``linear_wgrad_multi(sq=)``: the launch is the last writer of the gradient ``arena``
+    (every dw / db a view of it) and writes the grad-norm ``parts`` :func:`sqnorm` would (same
+    layout, scale 1, instead of that pass): each output tile the sum of squares of its final
+    values, extra workgroups the arena outside every target and outside ``lazy`` = (lo, hi)."""
+    parts: torch.Tensor
+    arena: torch.Tensor
+    lazy: Optional[tuple] = None
+
+
+class LnFinal(NamedTuple):
+    """The LayerNorm slot finalize (:func:`replica_reduce_` of ``ws`` [G, R, width] into the
+    addresses ``dst_ptrs``) riding in another launch (GPU only); ``store``: the destinations
+    get the sum instead of having it added.  ``offs`` (their element offsets in the gradient
+    arena): only the weight-gradient launch needs them, for its grad-norm partials."""
+    ws: torch.Tensor
+    dst_ptrs: torch.Tensor
+    width: int
+    rows: int
+    store: bool = False
+    offs: Optional[list] = None
+
+
+class EmbedGrads(NamedTuple):
+    """``linear_wgrad_multi(embed=)``: the cls / pos / time-embedding gradients of
+    :func:`embed_bwd` (``g`` .. ``dtemb`` as there; ``owners`` >= the distinct timesteps a
+    batch can hold) and, with ``ln``, the LayerNorm finalize ride in the launch as extra
+    workgroups (each writing the grad-norm partials of its outputs); the patch-row gradient
+    comes from the last LayerNorm backward (:func:`layernorm_bwd` ``gp_out``).  Deterministic."""
+    g: torch.Tensor
+    t: torch.Tensor
+    rng: torch.Tensor
+    site: int
+    p: float
+    dcls: torch.Tensor
+    dpos: torch.Tensor
+    dtemb: torch.Tensor
+    owners: int
+    ln: Optional[LnFinal] = None
+
+
+class StepTail(NamedTuple):
+    """``ln_fold_(tail=)``: the training step's tail rides in the fold launch -- the loss
+    from the smooth-L1 partials ``loss_parts`` (``loss_last``, and ``loss_ema`` with
+    ``ema_decay``) and the counter advance of :func:`advance_counters` on ``step`` / ``rng``
+    (optimizer step only if the grad norm ``sq`` is finite)."""
+    loss_parts: torch.Tensor
+    loss_last: Optional[torch.Tensor]
+    loss_ema: Optional[torch.Tensor]
+    ema_decay: float
+    step: torch.Tensor
+    rng: torch.Tensor
+    sq: Optional[torch.Tensor]
+
+
 def linear_wgrad_multi(jobs, store: bool = False, sq=None, embed=None, tickets=None):
     """Every ``(dy, x, dw, db)`` weight-gradient job of a step (<= 32) in ONE launch
     (csrc/gemm.hip ``gemm_wgrad_multi_kernel``; unsplit, deterministic).  ``store``:
     the targets are zero (``dW = dy^T x`` written, not added: no read of dW).
-
-    ``sq = (parts, arena, lazy)``: the launch is the last writer of the gradient
-    ``arena`` (every dw / db a view of it), so it also writes the grad-norm partials
-    :func:`sqnorm` would (same buffer layout, scale 1): each output tile the sum of
-    squares of its final values, extra workgroups the arena ranges outside every
-    target and outside ``lazy`` = (lo, hi).  Replaces the separate sqnorm pass.
-
-    ``embed = (g, t, rng, site, p, dcls, dpos, dtemb, owners, ln)``: the cls / pos /
-    time-embedding gradients of :func:`embed_bwd` (parts A, B; ``g`` the embedding
-    output gradient [B, N, D], ``owners`` >= the distinct timesteps a batch can hold)
-    and, with ``ln = (ws, dst_ptrs, offs, C, R, store)``, the LayerNorm slot finalize
-    ride in the same launch as extra workgroups (each writing the grad-norm partials of
-    its outputs); the patch-row gradient comes from the last LayerNorm backward
-    (:func:`layernorm_bwd` ``gp_out``).  Deterministic.
+    ``sq``: a :class:`GradNorm`; ``embed``: an :class:`EmbedGrads` (plain tuples of the
+    same order are taken too).
 
     ``tickets`` (:func:`wgrad_tickets`): reductions over >= 16,384 tokens run the tiles
     past the last whole round of workgroups as K pieces that take a ticket each.  Without
@@ -427,19 +470,26 @@ def linear_wgrad_multi(jobs, store: bool = False, sq=None, embed=None, tickets=N
     needs tickets raises.  ``torch.ops.ddim_cold.wgrad_multi_plan`` reports the launches."""
     if not jobs:
         return
+    sq = None if sq is None else GradNorm(*sq)
+    embed = None if embed is None else EmbedGrads(*embed)
+    ln = None if embed is None or embed.ln is None else LnFinal(*embed.ln)
+    if ln is not None and ln.offs is None:
+        raise ValueError("the LayerNorm finalize in the weight-gradient launch needs LnFinal.offs")
     if _hip(jobs[0][0]):  # (more than 32 jobs: consecutive launches of <= 32)
         dys, xs, dws, dbs = (list(z) for z in zip(*jobs))
-        parts, arena, (lo, hi) = (None, None, (0, 0)) if sq is None else \
-            (sq[0], sq[1], sq[2] if sq[2] is not None else (0, 0))
+        parts, arena, lazy = sq if sq is not None else (None, None, None)
+        lo, hi = lazy if lazy is not None else (0, 0)
         if embed is None:
             _ops().linear_wgrad_multi(dys, xs, dws, dbs, bool(store), parts, arena, int(lo), int(hi),
                                       split_tickets=tickets)
             return
-        g, t, rng, site, p, dcls, dpos, dtemb, owners, ln = embed
-        lw, lp, loffs, lC, lR, lst = ln if ln is not None else (None, None, [], 0, 0, False)
-        _ops().linear_wgrad_multi(dys, xs, dws, dbs, bool(store), parts, arena, int(lo), int(hi), g, t, rng,
-                                  int(site), float(p), dcls, dpos, dtemb, int(owners), lw, lp,
-                                  [int(o) for o in loffs], int(lC), int(lR), bool(lst), tickets)
+        e = embed
+        if ln is None:
+            ln = LnFinal(None, None, 0, 0, False, [])
+        _ops().linear_wgrad_multi(dys, xs, dws, dbs, bool(store), parts, arena, int(lo), int(hi), e.g, e.t, e.rng,
+                                  int(e.site), float(e.p), e.dcls, e.dpos, e.dtemb, int(e.owners), ln.ws,
+                                  ln.dst_ptrs, [int(o) for o in ln.offs], int(ln.width), int(ln.rows),
+                                  bool(ln.store), tickets)
         return
     for dy, x, dw, db in jobs:
         if store:
@@ -448,13 +498,11 @@ def linear_wgrad_multi(jobs, store: bool = False, sq=None, embed=None, tickets=N
                 db.zero_()
         ref.linear_wgrad(dy, x, dw, db)
     if embed is not None:
-        g, t, rng, site, p, dcls, dpos, dtemb, owners, ln = embed
-        ref.embed_bwd(g, t, rng, site, p, dcls, dpos, dtemb)
+        ref.embed_bwd(*embed[:8])
         if ln is not None:
             raise ValueError("the LayerNorm finalize in the weight-gradient launch needs the HIP extension")
     if sq is not None:
-        parts, arena, lazy = sq
-        sqnorm(arena, parts, 1.0, lazy=lazy)
+        sqnorm(sq.arena, sq.parts, 1.0, lazy=sq.lazy)
 
 
 def transpose_bf16_(srcs, dsts):
@@ -510,26 +558,22 @@ def ln_fold_(ws, gammas, betas, biases, wfs, cs, bfs, tail=None):
     """LayerNorm fold weights for GEMMs that consume a LayerNorm (one launch on GPU):
     ``wf = bf16(gamma o W)``, ``c = rowsum(wf)``, ``bf = b + W beta``.
 
-    ``tail = (loss_parts, loss_last, loss_ema, ema_decay, step, rng, sq)``: the
-    training step's tail rides in the same launch -- loss from the smooth-L1
-    partials (``loss_last``, EMA) and the counter advance of
-    :func:`advance_counters` (optimizer step only if the grad norm ``sq`` is finite)."""
+    ``tail``: a :class:`StepTail`, the training step's tail in the same launch."""
     if not ws:
         return
+    t = StepTail(*tail) if tail is not None else StepTail(None, None, None, 0.99, None, None, None)
     if _hip(ws[0]):
-        t = tail if tail is not None else (None, None, None, 0.99, None, None, None)
         return _ops().ln_fold_(list(ws), list(gammas), list(betas), list(biases), list(wfs), list(cs), list(bfs),
-                               t[0], t[1], t[2], float(t[3]), t[4], t[5], t[6])
+                               t.loss_parts, t.loss_last, t.loss_ema, float(t.ema_decay), t.step, t.rng, t.sq)
     for w, g, be, b, wf, c, bf in zip(ws, gammas, betas, biases, wfs, cs, bfs):
         ref.ln_fold(w, g, be, b, wf, c, bf)
     if tail is not None:
-        parts, loss_last, loss_ema, decay, step, rng, sq = tail
-        loss = parts.float().sum().reshape(1)
-        if loss_last is not None:
-            loss_last.copy_(loss.reshape(loss_last.shape))
-        if loss_ema is not None:
-            loss_ema.mul_(decay).add_(loss.reshape(loss_ema.shape), alpha=1.0 - decay)
-        advance_counters(step, rng, sq)
+        loss = t.loss_parts.float().sum().reshape(1)
+        if t.loss_last is not None:
+            t.loss_last.copy_(loss.reshape(t.loss_last.shape))
+        if t.loss_ema is not None:
+            t.loss_ema.mul_(t.ema_decay).add_(loss.reshape(t.loss_ema.shape), alpha=1.0 - t.ema_decay)
+        advance_counters(t.step, t.rng, t.sq)
 
 
 def replica_reduce_(ws, dst_ptrs, C: int, R: int, dsts=None):
@@ -554,14 +598,12 @@ def attn_bwd(do, qkv, o, lse, scale: float, rng, site: int, p: float, keep=None)
 
 
 def embed_bwd(g, t, rng, site: int, p: float, dcls, dpos, dtemb, ln_final=None):
-    """``ln_final = (ws, dst_ptrs, C, R[, store])``: the LayerNorm finalize
-    (:func:`replica_reduce_`) rides in the same launch (GPU only); ``store``: the
-    destinations get the sum instead of having it added.  Deterministic: no fp32
-    atomics (the time-embedding rows are summed per distinct timestep)."""
+    """``ln_final``: an :class:`LnFinal` riding in the same launch.  Deterministic: no
+    fp32 atomics (the time-embedding rows are summed per distinct timestep)."""
     if _hip(g):
-        ws, ptrs, C, R = ln_final[:4] if ln_final is not None else (None, None, 0, 0)
-        store = bool(ln_final[4]) if ln_final is not None and len(ln_final) > 4 else False
-        return _ops().embed_bwd(g, t, rng, site, float(p), dcls, dpos, dtemb, ws, ptrs, int(C), store, int(R))
+        ln = LnFinal(*ln_final) if ln_final is not None else LnFinal(None, None, 0, 0)
+        return _ops().embed_bwd(g, t, rng, site, float(p), dcls, dpos, dtemb, ln.ws, ln.dst_ptrs, int(ln.width),
+                                bool(ln.store), int(ln.rows))
     if ln_final is not None:
         raise ValueError("ln_final needs the HIP extension (use replica_reduce_ on CPU)")
     return ref.embed_bwd(g, t, rng, site, p, dcls, dpos, dtemb)
@@ -628,7 +670,6 @@ def adamw_step(p, g, m, v, pbf, sq, step, hyper, grad_scale: float = 1.0, zero_h
             raise RuntimeError("adamw_step: ema must be fp32 of the arena's size")
         if not 0.0 <= float(ema_decay) < 1.0:
             raise RuntimeError(f"adamw_step: ema_decay must be in [0, 1), got {ema_decay}")
-    import math
     sqv = float(sq.sum())
     base_lr, b1, b2, eps, wd, max_norm, tmax, eta_min = (float(x) for x in hyper.tolist()[:8])
     coef = grad_scale
@@ -662,7 +703,6 @@ def adamw_step(p, g, m, v, pbf, sq, step, hyper, grad_scale: float = 1.0, zero_h
 def advance_counters(step, rng, sq=None):
     if _hip(step):
         return _ops().advance_counters(step, rng, sq)
-    import math
     if sq is None or math.isfinite(float(sq.sum())):
         step[0] += 1
     step[1] += 1

@@ -52,7 +52,7 @@ import torch.distributed as dist
 
 from .. import ops
 from ..models import program as _program
-from ..models.program import LnFold, ModelTensors, ViTProgram, collect, is_matrix_param
+from ..models.program import BackwardPlan, LnFold, ModelTensors, ViTProgram, collect, is_matrix_param
 
 ALIGN = 64  # elements (256 B fp32)
 # Step graphs are captured in thread-local mode: other threads' HIP calls during a
@@ -80,6 +80,12 @@ FUSE_SQNORM = True
 # LayerNorm finalize run as extra workgroups of the weight-gradient launch
 # (csrc/embed_parts.h; False: embed_bwd as its own launch; tests compare the two)
 FUSE_EMBED_WGRAD = True
+# one micro-batch with the LayerNorm finalize in the embedding launch: everything above
+# ``acc_hi`` in the gradient arena (LayerNorms, blocks, head) is written by exactly one
+# producer per step, which then stores instead of adding -- the optimizer zeroes only the
+# embeddings and the deferred launches read no gradients; the all-reduce sums the fresh
+# values in place (False: accumulate + zero everything; tests compare the two)
+GRAD_OVERWRITE = True
 # models of at least this many tokens per sample (vit_small_200: 626) keep transposed bf16
 # shadows of the QKV / proj / fc1 / fc2 weights, re-transposed after every optimizer step, so
 # their input-gradient GEMMs run on the k-contiguous operand path
@@ -219,6 +225,58 @@ def _align(n: int) -> int:
     return (n + ALIGN - 1) // ALIGN * ALIGN
 
 
+@dataclass(frozen=True)
+class Switches:
+    """The module switches above, as read when a :class:`StepPlan` is built."""
+    ln_final: bool = True
+    sqnorm: bool = True
+    embed_wgrad: bool = True
+    overwrite: bool = True
+
+
+def step_decisions(cfg: EngineConfig, sw: Switches, world: int, segmented: bool, is_cuda: bool, B: int,
+                   has_temb_grad: bool) -> Dict[str, bool]:
+    """The step's fusion decisions, from the configuration alone (no tensors):
+
+    * ``merge``: without a separate embedding bucket (single process) the patch-embedding
+      weight gradient joins block 0's grouped launch;
+    * ``ln_final``: the LayerNorm replica finalize rides in the embedding-backward launch
+      (data parallel too: every LayerNorm lives in the last bucket's arena range);
+    * ``overwrite``: see ``GRAD_OVERWRITE``;
+    * ``fuse_sq``: single process, one micro-batch -- the one deferred weight-gradient launch
+      is the last writer of the gradient arena and writes the grad-norm partials too;
+    * ``embed_fused``: see ``FUSE_EMBED_WGRAD`` (its workgroups index a batch of <= 256)."""
+    merge = not (segmented and cfg.embed_bucket)
+    ln_final = is_cuda and sw.ln_final
+    overwrite = sw.overwrite and ln_final and max(1, int(cfg.grad_accum)) == 1
+    fuse_sq = sw.sqnorm and overwrite and not segmented and world == 1
+    embed_fused = fuse_sq and sw.embed_wgrad and merge and has_temb_grad and B <= 256
+    return dict(merge=merge, ln_final=ln_final, overwrite=overwrite, fuse_sq=fuse_sq, embed_fused=embed_fused)
+
+
+@dataclass(frozen=True)
+class StepPlan:
+    """Every decision of one optimizer step at one batch size (:meth:`TrainEngine._plan`),
+    with the bundles built from them.  ``tail``: the loss bookkeeping and counter advance
+    ride in the LayerNorm-fold launch after the optimizer; ``fused_loss``: the head GEMM's
+    epilogue computes the loss partials and the token-layout gradient; ``fuse_batch``: a
+    batch source with ``fused_spec()`` is drawn inside the patch-embedding launch;
+    ``flush_at``: the blocks after which a gradient bucket's weight gradients are issued
+    (None: single process, one launch after the backward); ``embed_owners``: the time
+    embedding rows of ``embed_fused``, else None; the rest as in :func:`step_decisions`."""
+    k_acc: int
+    tail: bool
+    fused_loss: bool
+    fuse_batch: bool
+    merge: bool
+    flush_at: Optional[frozenset]
+    overwrite: bool
+    fuse_sq: bool
+    embed_owners: Optional[int]
+    ln_final: Optional[ops.LnFinal]
+    backward: BackwardPlan
+
+
 class TrainEngine:
     def __init__(self, model, cfg: EngineConfig = EngineConfig(), device=None, process_group=None):
         self.cfg = cfg
@@ -275,6 +333,7 @@ class TrainEngine:
         self._graphs: Optional[List[torch.cuda.CUDAGraph]] = None
         self._mode: Optional[str] = None  # how _graphs replay: SINGLE / EVENT_SPLIT / SEGMENTS
         self._multi = None  # (K-step graph, K) for train_steps
+        self._plans: Dict[int, StepPlan] = {}  # _plan(): by batch size
         self._signal = None  # event-split step with a comm stream: the buckets' FlagSignal
         # event-split step: "pre-issued" / "post-replay" (comm stream), "inline" (none)
         self.handoff_order: Optional[str] = None
@@ -373,17 +432,20 @@ class TrainEngine:
         phase("native-comm:fallback-torch", error=self.native_error)
         return None
 
-    def _comm_host_async(self) -> bool:
-        """True when issuing a collective never blocks the host on device progress
-        (RCCL: ours or ProcessGroupNCCL).  gloo with CUDA tensors waits on the host for
-        its device-to-host copy, so its collectives must not be queued ahead of the
-        compute graph they wait for."""
+    def _comm_rccl(self) -> bool:
+        """Are the gradient collectives RCCL's (our communicator, ProcessGroupNCCL) or the
+        device loopback pair's?  Under either name below: issuing one never blocks the host
+        on device progress, and it can be captured into a hipGraph.  gloo with CUDA tensors
+        waits on the host for its device-to-host copy -- its collectives must not be queued
+        ahead of the compute graph they wait for -- and aborts the process inside a capture."""
         if self.ncomm is not None:
             return True
         try:
             return dist.get_backend(self.pg) == "nccl"
-        except Exception:  # pragma: no cover
+        except Exception:  # pragma: no cover - no process group
             return False
+
+    _comm_host_async = _comm_capturable = _comm_rccl
 
     def check_comm(self):
         """Raise ``RuntimeError`` if a comm-stream hand-off wait timed out (FlagSignal):
@@ -577,6 +639,7 @@ class TrainEngine:
             return
         if self.is_cuda and torch.cuda.is_current_stream_capturing():
             raise RuntimeError("the batch size changed inside a graph capture (LayerNorm workspace)")
+        self._plans.clear()  # they hold views of the buffers replaced here
         self.ln_ws = torch.zeros(len(self.ln_order), rows, 2 * D, dtype=torch.float32, device=self.device)
         self.ln_R = rows
         if self.sqnorm.numel() < nparts:
@@ -659,132 +722,117 @@ class TrainEngine:
         self.batch_fn = fn
         self._drop_capture(rewarm=False)
 
-    def _grad_overwrite(self, k_acc: int, deferred: bool, ln_final) -> bool:
-        """One micro-batch, deferred weight gradients (the single-process tail launch or
-        one launch per data-parallel bucket) and the LayerNorm finalize in the
-        embedding launch: everything above ``acc_hi`` in the gradient arena
-        (LayerNorms, blocks, head) is written by exactly one producer per step, which
-        then stores instead of adding -- the optimizer zeroes only the embeddings
-        (accumulated by atomics) and the deferred launches read no gradients.  The
-        all-reduce sums the fresh values in place."""
-        return self.is_cuda and k_acc == 1 and deferred and ln_final is not None
+    @property
+    def _fuse_batch(self) -> bool:
+        return self.cfg.fuse_batch and self.lnfold is not None and self.prog.supports_fused_loss(self.param_tensors)
+
+    def _plan(self, B: int) -> StepPlan:
+        """The step's decisions at batch size ``B``, cached until the capture is dropped or
+        the batch buffers (whose views the plan holds) are reallocated."""
+        self._ensure_batch_buffers(B)
+        plan = self._plans.get(B)
+        if plan is None:
+            c, cfg = self.prog.cfg, self.cfg
+            sw = Switches(FUSE_LN_FINAL, FUSE_SQNORM, FUSE_EMBED_WGRAD, GRAD_OVERWRITE)
+            d = step_decisions(cfg, sw, self.world, self.segmented, self.is_cuda, B,
+                               self.grad_tensors.temb is not None)
+            tail = self.lnfold is not None
+            hi = self.ln_done_at[-1]
+            ln_final = ops.LnFinal(self.ln_ws[:hi], self.ln_ptrs[:hi], 2 * c.dim, self.ln_R, d["overwrite"],
+                                   self._ln_offs()[:hi]) if d["ln_final"] else None
+            flush_at = frozenset(k for k in self.bucket_after if k >= 0) if self.segmented else None
+            owners = self._emb_owners(B) if d["embed_fused"] else None
+            bwd = BackwardPlan(ln_ws=self.ln_ws, embed_with_block0=d["merge"], ln_final=ln_final, flush_at=flush_at,
+                               store=d["overwrite"], owners=owners, tickets=self.wgrad_tickets,
+                               grad_norm=ops.GradNorm(self.sqnorm, self.opt_g, self.lazy) if d["fuse_sq"] else None)
+            plan = self._plans[B] = StepPlan(
+                k_acc=max(1, int(cfg.grad_accum)), tail=tail,
+                fused_loss=tail and self.prog.supports_fused_loss(self.param_tensors), fuse_batch=self._fuse_batch,
+                merge=d["merge"], flush_at=flush_at, overwrite=d["overwrite"], fuse_sq=d["fuse_sq"],
+                embed_owners=owners, ln_final=ln_final, backward=bwd)
+        return plan
 
     def _step_iter(self):
-        c = self.prog.cfg
-        k_acc = max(1, int(self.cfg.grad_accum))
-        # loss bookkeeping + counter advance ride in the LayerNorm-fold launch after
-        # the optimizer (one workgroup of it) instead of two extra tiny launches.
-        # With grad_accum > 1 the micro-batch loss partials are averaged first, so the
-        # EMA moves once per optimizer step (multi_gpu_trainer.py:126 semantics).
-        tail = self.lnfold is not None
-        loss_acc = None
-        overwrite = False
+        """One optimizer step: yields ``("bucket", k)`` when gradient bucket ``k`` is final
+        (last micro-batch) and ``("done", -1)`` after the optimizer."""
         self._temb_t = []
+        k_acc = max(1, int(self.cfg.grad_accum))
+        loss_parts = None
         for micro in range(k_acc):
-            last = micro == k_acc - 1
             if micro > 0:
                 self.rng[1:].add_(1)  # fresh dropout masks and batch draws per micro-batch
-            fused_loss = tail and self.prog.supports_fused_loss(self.param_tensors)
             spec = getattr(self.batch_fn, "fused_spec", None)
-            cold = None
-            if fused_loss and self.cfg.fuse_batch and spec is not None:
-                (img, tgt, t), cold = spec()  # drawn inside the patch-embedding launch
+            # (a fused spec is drawn inside the patch-embedding launch)
+            batch, cold = spec() if self._fuse_batch and spec is not None else (self.batch_fn(), None)
+            plan = self._plan(int(batch[2].shape[0]))
+            loss_parts = yield from self._micro_batch(plan, batch, cold, micro == k_acc - 1, loss_parts)
+        self._optimizer_tail(plan, loss_parts)
+        yield ("done", -1)
+
+    def _micro_batch(self, plan: StepPlan, batch, cold, last: bool, loss_acc):
+        """Forward, loss and backward of one micro-batch, yielding at the gradient bucket
+        boundaries of the ``last`` one; returns the step's loss partials so far.  With
+        grad_accum > 1 the micro-batch partials are averaged, so the loss EMA moves once
+        per optimizer step (multi_gpu_trainer.py:126 semantics)."""
+        c, cfg = self.prog.cfg, self.cfg
+        img, tgt, t = batch
+        self._temb_t.append(t)
+        if plan.fused_loss:
+            (loss_parts, dtok), S = self.prog.forward(self.param_tensors, img, t, self.rng, True,
+                                                      loss=(tgt, cfg.loss_beta), cold=cold)
+        else:
+            out, S = self.prog.forward(self.param_tensors, img, t, self.rng, True)
+            if plan.tail or plan.k_acc > 1:
+                loss_parts, dtok = ops.smooth_l1_fwd_bwd(out, tgt, c.tokens, c.patch, cfg.loss_beta, finish=False)
             else:
-                img, tgt, t = self.batch_fn()
-            self._temb_t.append(t)
-            self._ensure_batch_buffers(int(t.shape[0]))
-            if fused_loss:
-                # head GEMM epilogue computes the loss partials and the token-layout gradient
-                (loss_parts, dtok), S = self.prog.forward(self.param_tensors, img, t, self.rng, True,
-                                                          loss=(tgt, self.cfg.loss_beta), cold=cold)
-                out = None
-            else:
-                out, S = self.prog.forward(self.param_tensors, img, t, self.rng, True)
-            if out is None:
-                pass
-            elif tail or k_acc > 1:
-                loss_parts, dtok = ops.smooth_l1_fwd_bwd(out, tgt, c.tokens, c.patch, self.cfg.loss_beta,
-                                                         finish=False)
-            else:
-                _, dtok = ops.smooth_l1_fwd_bwd(out, tgt, c.tokens, c.patch, self.cfg.loss_beta, self.loss_last,
-                                                self.loss_ema, self.cfg.ema_decay)
+                loss_parts = None  # finished here: loss_last and its EMA
+                _, dtok = ops.smooth_l1_fwd_bwd(out, tgt, c.tokens, c.patch, cfg.loss_beta, self.loss_last,
+                                                self.loss_ema, cfg.ema_decay)
             del out
-            if k_acc > 1:  # mean over micro-batches (partials sum to each micro-batch's loss)
-                lp = loss_parts.float() * (1.0 / k_acc)
-                loss_acc = lp if loss_acc is None else loss_acc + lp
-            ln_lo = 0
-            # without a separate embedding bucket (single process) the patch-embedding
-            # weight gradient joins block 0's grouped launch
-            merge = not (self.segmented and self.cfg.embed_bucket)
-            # the LayerNorm replica finalize rides in the embedding-backward launch (data
-            # parallel too: every LayerNorm lives in the last bucket's arena range)
-            ln_final = None
-            if self.ln_ptrs is not None and FUSE_LN_FINAL:
-                hi = self.ln_done_at[-1]
-                ln_final = (self.ln_ws[:hi], self.ln_ptrs[:hi], 2 * c.dim, self.ln_R)
-            # single process: every weight gradient in one launch after the backward (no
-            # bucket needs a block's gradients early); data parallel: one launch per
-            # gradient bucket, so its all-reduce can start while the backward goes on
-            flush_at = set(k for k in self.bucket_after if k >= 0) if self.segmented else None
-            # one micro-batch: every gradient above the embeddings has ONE producer per
-            # step (the deferred weight-gradient launches, the LayerNorm finalize), so those
-            # write instead of accumulate and the optimizer zeroes only the embeddings
-            overwrite = self._grad_overwrite(k_acc, True, ln_final)
-            if overwrite:
-                ln_final = ln_final + (True,)
-            # single process, one micro-batch: the deferred weight-gradient launch is the
-            # last writer of the gradient arena and writes the grad-norm partials too
-            fuse_sq = (FUSE_SQNORM and overwrite and flush_at is None and k_acc == 1 and self.world == 1
-                       and self.is_cuda)
-            B = int(t.shape[0])
-            emb_fused = None
-            if (fuse_sq and FUSE_EMBED_WGRAD and merge and self.grad_tensors.temb is not None and B <= 256
-                    and ln_final is not None):
-                emb_fused = (self._emb_owners(B), self._ln_offs()[:ln_final[1].numel()])
-            for i in self.prog.backward_iter(self.param_tensors, self.grad_tensors, S, dtok, self.rng, True,
-                                             ln_ws=self.ln_ws, embed_with_block0=merge, ln_final=ln_final,
-                                             wgrad_flush=flush_at, wgrad_store=overwrite,
-                                             wgrad_sq=(self.sqnorm, self.opt_g, self.lazy) if fuse_sq else None,
-                                             embed_fused=emb_fused, wgrad_tickets=self.wgrad_tickets):
-                if i in self.bucket_after and (self.segmented or i == -1):
-                    hi = self.ln_done_at[i]
-                    if ln_final is not None:
-                        ln_lo = hi  # already finalized by the embedding backward
-                    if hi > ln_lo:
-                        ops.replica_reduce_(self.ln_ws[ln_lo:hi],
-                                            None if self.ln_ptrs is None else self.ln_ptrs[ln_lo:hi],
-                                            2 * c.dim, self.ln_R, dsts=self.ln_dsts[ln_lo:hi])
-                        ln_lo = hi
-                    if last:
-                        yield ("bucket", self.bucket_after[i])
-            S = None
-        # optimizer: grads are SUM-reduced over ranks and summed over micro-batches
-        # -> average via grad_scale
-        gs = 1.0 / (self.world * k_acc)
-        if not fuse_sq:
+        if plan.k_acc > 1:  # mean over micro-batches (partials sum to each micro-batch's loss)
+            lp = loss_parts.float() * (1.0 / plan.k_acc)
+            loss_parts = lp if loss_acc is None else loss_acc + lp
+        ln_lo = 0
+        for i in self.prog.backward_iter(self.param_tensors, self.grad_tensors, S, dtok, self.rng, True,
+                                         plan=plan.backward):
+            if i in self.bucket_after and (self.segmented or i == -1):
+                hi = self.ln_done_at[i]
+                if plan.ln_final is not None:
+                    ln_lo = hi  # already finalized by the embedding backward
+                if hi > ln_lo:
+                    ops.replica_reduce_(self.ln_ws[ln_lo:hi], None if self.ln_ptrs is None else self.ln_ptrs[ln_lo:hi],
+                                        2 * c.dim, self.ln_R, dsts=self.ln_dsts[ln_lo:hi])
+                    ln_lo = hi
+                if last:
+                    yield ("bucket", self.bucket_after[i])
+        return loss_parts
+
+    def _optimizer_tail(self, plan: StepPlan, loss_parts):
+        """Grad norm (unless the weight-gradient launch wrote it), AdamW, the transposed
+        shadows, then the LayerNorm fold carrying the loss bookkeeping and counter advance
+        (:class:`ops.StepTail`) or those as launches of their own."""
+        cfg = self.cfg
+        # grads are SUM-reduced over ranks and summed over micro-batches -> average via grad_scale
+        gs = 1.0 / (self.world * plan.k_acc)
+        if not plan.fuse_sq:
             ops.sqnorm(self.opt_g, self.sqnorm, gs, lazy=self.lazy)
-        if loss_acc is not None:
-            loss_parts = loss_acc
-        ema = {} if self.opt_e is None else dict(ema=self.opt_e, ema_decay=self.cfg.weight_ema,
-                                                 ema_warmup=self.cfg.weight_ema_warmup)
+        ema = {} if self.opt_e is None else dict(ema=self.opt_e, ema_decay=cfg.weight_ema,
+                                                 ema_warmup=cfg.weight_ema_warmup)
         ops.adamw_step(self.opt_p, self.opt_g, self.opt_m, self.opt_v, self.opt_pb, self.sqnorm,
-                       self.step_ctr, self.hyper, gs, zero_hi=self.acc_hi if overwrite else None,
+                       self.step_ctr, self.hyper, gs, zero_hi=self.acc_hi if plan.overwrite else None,
                        lazy=self.lazy, lazy_decay=self.lazy_decay, **ema)
         if self.wt is not None:  # the input-gradient GEMMs' transposed shadows of the new weights
             self.wt.refresh()
-        if tail:
-            self.lnfold.refresh(tail=(loss_parts, self.loss_last, self.loss_ema, self.cfg.ema_decay, self.step_ctr,
-                                      self.rng, self.sqnorm))
+        if plan.tail:
+            self.lnfold.refresh(tail=ops.StepTail(loss_parts, self.loss_last, self.loss_ema, cfg.ema_decay,
+                                                  self.step_ctr, self.rng, self.sqnorm))
         else:
-            if k_acc > 1:  # one EMA update per optimizer step
+            if plan.k_acc > 1:  # one EMA update per optimizer step
                 loss = loss_parts.sum().reshape(self.loss_last.shape)
                 self.loss_last.copy_(loss)
-                self.loss_ema.mul_(self.cfg.ema_decay).add_(loss, alpha=1.0 - self.cfg.ema_decay)
-            if self.lnfold is not None:
-                self.lnfold.refresh()
+                self.loss_ema.mul_(cfg.ema_decay).add_(loss, alpha=1.0 - cfg.ema_decay)
             ops.advance_counters(self.step_ctr, self.rng, self.sqnorm)
         self.prog._keep = None
-        yield ("done", -1)
 
     def _allreduce(self, k: int, wait_counter: bool = False):
         """Issue bucket ``k``'s collectives: on the comm stream, ordered after the
@@ -802,10 +850,10 @@ class TrainEngine:
             if many is not None and self.flat_gw is None and not fake and len(ranges) > 1:
                 # the bucket's ranges as one RCCL group: one launch
                 many([self.flat_g[a:b] for a, b in ranges])
-                if k == self.temb_bucket:
-                    self._temb_exchange()
-                return
-            for a, b in ranges:
+                todo = ()
+            else:
+                todo = ranges
+            for a, b in todo:
                 if fake:  # topology experiment at 1 rank: passes over the range stand in for the collective
                     self.flat_g[a:b].mul_(1.0)
                 elif self.ncomm is not None:
@@ -890,17 +938,6 @@ class TrainEngine:
             return (name, int(base[8:]), True, False)
         raise ValueError(f"unknown gradient-exchange layout {name!r} ([graph-]overlap-<blocks> or "
                          "[graph-]inline-1)")
-
-    def _comm_capturable(self) -> bool:
-        """Can the gradient collectives be captured into a hipGraph?  RCCL (our
-        communicator or ProcessGroupNCCL) and the device loopback pair can; gloo
-        stages CUDA tensors through the host and aborts the process inside a capture."""
-        if self.ncomm is not None:
-            return True
-        try:
-            return self.dist_on and dist.get_backend(self.pg) == "nccl"
-        except Exception:  # pragma: no cover
-            return False
 
     def apply_layout(self, layout):
         """Switch to a layout given by name or ``(name, bucket_blocks, embed_bucket,
@@ -1201,7 +1238,8 @@ class TrainEngine:
 
     def _drop_capture(self, rewarm: bool):
         """Forget the captured step: its graphs, the K-step graph, the hand-off
-        counters (``check_comm`` / ``comm_error`` then see none) and ``handoff_order``.
+        counters (``check_comm`` / ``comm_error`` then see none), ``handoff_order`` and the
+        cached step plans.
         The next ``train_step`` re-captures, after ``graph_warmup`` fresh eager steps
         if ``rewarm``.  Nothing else clears these fields."""
         self._graphs = None
@@ -1209,6 +1247,7 @@ class TrainEngine:
         self._multi = None
         self._signal = None
         self.handoff_order = None
+        self._plans.clear()
         if rewarm:
             self._eager_steps = 0
 
@@ -1514,20 +1553,16 @@ class TrainEngine:
         snapshot before taking the next."""
         self.materialize_lazy()
         cur = torch.cuda.current_stream(self.device) if self.is_cuda else None
+        src = (self.flat_p, self.flat_m, self.flat_v, self.step_ctr, self.rng)
+        if self.flat_e is not None:  # the weight EMA rides along as a sixth buffer
+            self._no_ema_scope("snapshot_to_host")
+            src += (self.flat_e,)
         if self._snap is None:
-            pin = self.is_cuda
-            like = (self.flat_p, self.flat_m, self.flat_v, self.step_ctr, self.rng)
-            if self.flat_e is not None:  # the weight EMA rides along as a sixth buffer
-                like += (self.flat_e,)
-            host = [torch.empty(t.shape, dtype=t.dtype, pin_memory=pin) for t in like]
-            dev = [torch.empty_like(t) for t in like] if self.is_cuda else None
+            host = [torch.empty(t.shape, dtype=t.dtype, pin_memory=self.is_cuda) for t in src]
+            dev = [torch.empty_like(t) for t in src] if self.is_cuda else None
             side = torch.cuda.Stream(self.device) if self.is_cuda else None
             self._snap = (host, dev, side)
         host, dev, side = self._snap
-        src = (self.flat_p, self.flat_m, self.flat_v, self.step_ctr, self.rng)
-        if self.flat_e is not None:
-            self._no_ema_scope("snapshot_to_host")
-            src += (self.flat_e,)
         ev = None
         if self.is_cuda:
             for d, t in zip(dev, src):
@@ -1632,15 +1667,7 @@ class HostSnapshot:
 
     def state_dict(self) -> Dict[str, torch.Tensor]:
         """The model's ``state_dict`` (parameter order and shapes) from the snapshot."""
-        eng = self.engine
-        shapes = {n: p.shape for n, p in eng.model.named_parameters()}
-        out = {}
-        for n in eng.model.state_dict().keys():
-            if n not in eng.offsets:
-                raise KeyError(f"{n}: not in the parameter arena (a buffer?) -- snapshot cannot hold it")
-            o, k = eng.offsets[n]
-            out[n] = self.p[o:o + k].view(shapes[n]).clone()
-        return out
+        return self.engine._arena_state_dict(self.p)
 
     def ema_state_dict(self) -> Dict[str, torch.Tensor]:
         """The EMA weights as the model's ``state_dict``, from the snapshot."""

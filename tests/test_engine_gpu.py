@@ -184,11 +184,10 @@ def test_ln_replica_finalize_fused_matches_separate(monkeypatch):
 def test_gradient_overwrite_matches_accumulate(monkeypatch):
     """Single writer per gradient range (tail weight-gradient launch and LayerNorm finalize
     store, AdamW zeroes only the embeddings) == accumulate + zero everything."""
-    orig = TrainEngine._grad_overwrite
+    from ddim_cold_amd.train import engine as engine_mod
 
     def run(flag):
-        monkeypatch.setattr(TrainEngine, "_grad_overwrite",
-                            orig if flag == "1" else (lambda self, *a, **k: False))
+        monkeypatch.setattr(engine_mod, "GRAD_OVERWRITE", flag == "1")
         torch.manual_seed(0)
         model = build_model("vit_tiny").cuda().train()
         eng = TrainEngine(model, EngineConfig(lr=1e-3, t_max=100, seed=3, use_graph=True, graph_warmup=1,

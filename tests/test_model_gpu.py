@@ -7,7 +7,7 @@ pytestmark = pytest.mark.gpu
 
 from ddim_cold_amd import ops
 from ddim_cold_amd.models import DiffusionVisionTransformer, build_model
-from ddim_cold_amd.models.program import ViTProgram, collect, model_tensors
+from ddim_cold_amd.models.program import BackwardPlan, ViTProgram, collect, model_tensors
 from ddim_cold_amd.ops import reference as ref
 
 DEV = "cuda"
@@ -88,10 +88,9 @@ def test_backward_wgrad_schedules_match(name, embed_with_block0, mode):
     for variant in ("tail", mode):
         grads = {n: torch.zeros_like(p) for n, p in m.named_parameters()}
         G = collect(grads, prog.cfg.depth, prog.cfg.dim)
-        kw = dict(embed_with_block0=embed_with_block0)
-        if variant == "bucket":
-            kw["wgrad_flush"] = {3, 1, 0}
-        elif variant == "immediate":
+        kw = dict(plan=BackwardPlan(embed_with_block0=embed_with_block0,
+                                    flush_at=frozenset({3, 1, 0}) if variant == "bucket" else None))
+        if variant == "immediate":
             kw["wgrad"] = ops.linear_wgrad
         with torch.no_grad():
             order = list(prog.backward_iter(P, G, S, dtok, r, True, **kw))

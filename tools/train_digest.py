@@ -1,0 +1,114 @@
+"""One ``case sha256`` line per training-step case, through the public engine API and the module
+switches alone: run on two trees (same built extension) and diff the output to show a change of
+the step code kept every arena bit for bit.  Each line hashes flat_p / flat_m / flat_v / flat_g,
+loss_last, loss_ema, step_ctr, rng and flat_e where present.  The data-parallel cases are the
+step of ONE engine (``force_segments``; on ``cuda`` with a one-replica stand-in communicator, on
+``cpu`` eager with nothing to exchange).  With an embedding bucket the patch-embedding weight
+gradient is summed by fp32 atomics (the token-split ``linear_wgrad``), so those cases do not
+reproduce themselves bit for bit: ``--dump DIR`` keeps every case's tensors and ``compare``
+checks two dumps under the engine tests' bound for last-bit gradient differences through AdamW
+(max |dp| <= 2 lr per step, loss within 1e-4 relative, counters equal).
+python tools/train_digest.py cpu|cuda [--dump DIR] [case ...]  |  compare DIR_A DIR_B"""
+import hashlib, os, sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+os.environ.setdefault("DDIM_COLD_HANDOFF_TIMEOUT_US", "500000")
+import torch
+from ddim_cold_amd import build_model
+from ddim_cold_amd.data.synthetic import ColdBatcher, GaussianBatcher, synthetic_pool
+from ddim_cold_amd.models import program
+from ddim_cold_amd.train import engine as engine_mod
+from ddim_cold_amd.train.engine import EngineConfig, TrainEngine
+
+args = sys.argv[1:]
+dev = args.pop(0) if args else "cpu"
+dump = args[1] if args[:1] == ["--dump"] else None
+args = args[2:] if dump else args
+cuda = dev == "cuda"
+LR = 1e-3
+KEYS = ("flat_p", "flat_m", "flat_v", "flat_g", "loss_last", "loss_ema", "step_ctr", "rng", "flat_e")
+SWITCHES = ("FUSE_LN_FINAL", "FUSE_SQNORM", "FUSE_EMBED_WGRAD", "GRAD_OVERWRITE")
+ORIG_OVERWRITE = getattr(TrainEngine, "_grad_overwrite", None)  # trees without the GRAD_OVERWRITE switch
+
+
+class SelfComm:
+    """A one-replica communicator: the sum over one rank, as a kernel on the caller's stream."""
+
+    def all_reduce_(self, buf, op=0):
+        buf.mul_(1.0)
+
+
+def set_switch(name: str, on: bool):
+    if name == "GRAD_OVERWRITE" and not hasattr(engine_mod, name):
+        TrainEngine._grad_overwrite = ORIG_OVERWRITE if on else (lambda self, *a, **k: False)
+    else:
+        setattr(engine_mod, name, on)
+
+
+def case(label, steps=3, off=None, fold=True, name="vit_tiny", model_kw=None, size=64, B=8, gauss=False, layout=None,
+         **cfg):
+    for s in SWITCHES:
+        set_switch(s, s != off)
+    program.FOLD_LN = fold
+    torch.manual_seed(0)
+    model = build_model(name, **(model_kw or {})).to(dev).train()
+    cfg = dict(dict(lr=LR, t_max=100, seed=3, use_graph=False, graph_warmup=1, temb_rows=7), **cfg)
+    eng = TrainEngine(model, EngineConfig(**cfg), device=dev)
+    if cfg.get("force_segments"):
+        if cuda:
+            eng.attach_comm(SelfComm(), 1)
+        if layout is not None:
+            eng.apply_layout(layout)
+    pool = synthetic_pool(64, size=(size, size), seed=1, device=dev)
+    eng.set_batch_fn(GaussianBatcher(pool, B, eng.rng, 2000) if gauss else ColdBatcher(pool, B, eng.rng))
+    eng.train_steps(steps)
+    if cuda:
+        torch.cuda.synchronize()
+    h = hashlib.sha256()
+    state = {k: getattr(eng, k).detach().cpu().contiguous() for k in KEYS if getattr(eng, k, None) is not None}
+    for t in state.values():
+        h.update(t.numpy().tobytes())
+    if dump is not None:
+        os.makedirs(dump, exist_ok=True)
+        torch.save(state, os.path.join(dump, label.replace(" ", "_") + ".pt"))
+    eng.detach()
+    return h.hexdigest()[:32]
+
+
+G = dict(use_graph=True)  # (ignored on cpu: the same steps run eagerly)
+DP = dict(force_segments=True, steps=4, **G)
+CASES = {
+    "eager": dict(),
+    "graph": dict(steps=5, **G),
+    "graph_steps=4": dict(steps=9, graph_steps=4, **G),
+    "grad_accum=2": dict(grad_accum=2, **G),
+    "fuse_batch=False": dict(fuse_batch=False, **G),
+    **{f"{s} off": dict(off=s, **G) for s in SWITCHES},
+    "clipped": dict(max_grad_norm=0.1, **G),  # (clipping active: the grad norm moves every parameter)
+    **{f"{s} off, clipped": dict(off=s, max_grad_norm=0.1, **G) for s in SWITCHES},
+    "FOLD_LN off": dict(fold=False, **G),
+    "weight_ema=0.99": dict(weight_ema=0.99, **G),
+    "gaussian temb_rows=None": dict(gauss=True, temb_rows=None, **G),
+    "frozen time embedding": dict(model_kw=dict(timestep_embedding="sinusoidal"), **G),
+    "vit_small_200 depth 2": dict(name="vit_small_200", model_kw=dict(depth=2), size=200, B=2, **G),
+    "dp overlap-2": dict(layout="overlap-2", **DP),
+    "dp inline-1": dict(layout="inline-1", **DP),
+    "dp graph-overlap-2": dict(layout="graph-overlap-2", **DP),
+    "dp segments": dict(comm_events=False, graph_comm=False, **DP),
+    # the same three capture modes without the embedding bucket (no atomics: hashes reproduce)
+    "dp event-split, no embed bucket": dict(embed_bucket=False, **DP),
+    "dp captured, no embed bucket": dict(embed_bucket=False, comm_events=False, **DP),
+    "dp segments, no embed bucket": dict(embed_bucket=False, comm_events=False, graph_comm=False, **DP),
+}
+if dev == "compare":
+    for f in sorted(os.listdir(args[0])):
+        a, b = (torch.load(os.path.join(d, f)) for d in args[:2])
+        steps = int(a["step_ctr"][0])
+        dp, dl = float((a["flat_p"] - b["flat_p"]).abs().max()), float((a["loss_last"] - b["loss_last"]).abs())
+        ok = (dp <= 2 * LR * steps and dl <= 1e-4 * float(b["loss_last"].abs())
+              and all(torch.equal(a[k], b[k]) for k in ("step_ctr", "rng")))
+        print(f"{f[:-3]}: max |dp| {dp:.3g} (bound {2 * LR * steps:.3g}), |dloss| {dl:.3g} "
+              f"{'ok' if ok else 'FAIL'}", flush=True)
+    sys.exit(0)
+for label, kw in CASES.items():
+    if not args or label in args:
+        print(f"{label} {case(label, **kw)}", flush=True)
