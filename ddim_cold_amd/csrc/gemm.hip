@@ -421,230 +421,103 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_dma_kernel(GemmParams p) {
   gemm_dma_body<BM, BN, WM, WN, AT, BT, EPI, S>(p, tm, bid - tm * tiles_n, blockIdx.z);
 }
 
-// Ring depth of the LDS-DMA GEMM for BM x BN tiles (the one rule: launch_dma launches
-// by it, gemm_dma_plan reports it).  Keep every workgroup of the grid co-resident (one
-// round): a 4-stage ring allows 160 KiB / (4 x stage) workgroups per CU, a 3-stage ring
-// 4/3 of that; 256x128 fits 3 stages only, 256x192 only 2.
-static int dma_ring_stages(int bm, int bn, int workgroups, int ktiles_per_split) {
-  const int stage = bm * 128 + bn * 128;
-  if (3 * stage > 160 * 1024) return 2;
-  if (4 * stage > 160 * 1024) return 3;
-  const int per_cu4 = (160 * 1024) / (4 * stage);
-  return workgroups > 256 * per_cu4 && ktiles_per_split <= 8 ? 3 : 4;
+// The kernels of the main GEMM family, listed once: the explicit instantiations and the
+// launch switch below are both generated from these lists, and which kernel a problem gets
+// is gemm_plan's decision alone (gemm_plan.h).  A macro list because hipcc 7.2 needs
+// explicit instantiations at namespace scope: it intermittently fails to emit host launch
+// stubs for implicitly instantiated kernel templates (undefined __device_stub__ at dlopen;
+// build.py also checks the .so for that) and silently drops the stub of a kernel template
+// first referenced inside an if-constexpr branch.
+//
+// Ring kernels, X(AT, BT, EPI, BM, BN, WM, WN, S), one line per family.  Every entry is
+// checked against gemm_kernel_built and their number against gemm_kernels_built(): the list
+// is the predicate's set, no more and no less.
+#define DC_S34(X, AT, BT, EPI, BM, BN, WM, WN) X(AT, BT, EPI, BM, BN, WM, WN, 3) X(AT, BT, EPI, BM, BN, WM, WN, 4)
+#define DC_BN64(X, AT, BT, EPI) \
+  DC_S34(X, AT, BT, EPI, 32, 64, 2, 2) DC_S34(X, AT, BT, EPI, 64, 64, 2, 2) DC_S34(X, AT, BT, EPI, 128, 64, 2, 2)
+#define DC_NT4(X, EPI) DC_BN64(X, false, false, EPI) DC_S34(X, false, false, EPI, 128, 128, 2, 2)
+#define DC_W8_128(X, BT, EPI) DC_S34(X, false, BT, EPI, 128, 128, 4, 2)
+#define DC_W8(X, BT, EPI) X(false, BT, EPI, 256, 128, 4, 2, 3) DC_W8_128(X, BT, EPI)
+#define DC_W192(X, EPI) X(false, false, EPI, 256, 192, 4, 2, 2)
+#define DC_RING_KERNELS(X)                                               \
+  DC_NT4(X, EPI_BF16) DC_W8(X, false, EPI_BF16) DC_W192(X, EPI_BF16)     \
+  DC_NT4(X, EPI_F32) DC_W8(X, false, EPI_F32)                            \
+  DC_NT4(X, EPI_QKV) DC_W8(X, false, EPI_QKV) DC_W192(X, EPI_QKV)        \
+  DC_NT4(X, EPI_RESID) DC_W8(X, false, EPI_RESID)                        \
+  DC_NT4(X, EPI_GELU) DC_W8(X, false, EPI_GELU) DC_W192(X, EPI_GELU)     \
+  DC_NT4(X, EPI_HEAD)                                                    \
+  DC_NT4(X, EPI_EMBED) DC_W8(X, false, EPI_EMBED)                        \
+  DC_NT4(X, EPI_DGELU) DC_W8_128(X, false, EPI_DGELU) /* k-contiguous: transposed weight shadow */ \
+  DC_NT4(X, EPI_HEADR)                                                   \
+  DC_NT4(X, EPI_HEADL)                                                   \
+  DC_NT4(X, EPI_HEADRS)                                                  \
+  DC_BN64(X, false, true, EPI_BF16) DC_W8(X, true, EPI_BF16)             \
+  DC_BN64(X, false, true, EPI_F32) DC_W8(X, true, EPI_F32)               \
+  DC_BN64(X, false, true, EPI_DGELU) DC_W8_128(X, true, EPI_DGELU)       \
+  DC_S34(X, true, true, EPI_ATOMIC, 64, 64, 2, 2)
+// The plain (K % 64 != 0) kernel, X(AT, BT, EPI): both of its tiles for every family.
+#define DC_FAMILIES(X)                                                                              \
+  X(false, false, EPI_BF16) X(false, false, EPI_F32) X(false, false, EPI_QKV) X(false, false, EPI_RESID) \
+  X(false, false, EPI_GELU) X(false, false, EPI_HEAD) X(false, false, EPI_EMBED) X(false, false, EPI_DGELU) \
+  X(false, false, EPI_HEADR) X(false, false, EPI_HEADL) X(false, false, EPI_HEADRS)                 \
+  X(false, true, EPI_BF16) X(false, true, EPI_F32) X(false, true, EPI_DGELU) X(true, true, EPI_ATOMIC)
+
+#define DC_INST_RING(AT, BT, EPI, BM, BN, WM, WN, S)                                              \
+  static_assert(gemm_kernel_built(AT, BT, EPI, BM, BN, WM * WN, S), "a ring kernel outside gemm_kernel_built"); \
+  template __global__ void gemm_dma_kernel<BM, BN, WM, WN, AT, BT, EPI, S>(GemmParams);
+#define DC_INST_PLAIN(AT, BT, EPI)                                                                \
+  static_assert(gemm_family_built(AT, BT, EPI), "a plain kernel outside gemm_family_built");      \
+  template __global__ void gemm_kernel<32, 64, 2, 2, AT, BT, EPI>(GemmParams);                    \
+  template __global__ void gemm_kernel<64, 64, 2, 2, AT, BT, EPI>(GemmParams);
+#define DC_COUNT(...) +1
+DC_RING_KERNELS(DC_INST_RING)
+DC_FAMILIES(DC_INST_PLAIN)
+static_assert(0 DC_RING_KERNELS(DC_COUNT) == gemm_kernels_built(), "a kernel of gemm_kernel_built is not in the list");
+#undef DC_INST_RING
+#undef DC_INST_PLAIN
+#undef DC_COUNT
+
+// one integer per kernel of the lists (every field within its radix for the tiles of gemm_plan.h)
+constexpr int kernel_key(bool at, bool bt, int epi, int bm, int bn, int waves, int stages) {
+  return ((((((int)at * 2 + (int)bt) * 16 + epi) * 16 + bm / 32) * 4 + bn / 64) * 4 + waves / 4) * 8 + stages;
 }
 
-template <int BM, int BN, int WM, int WN, bool AT, bool BT, int EPI>
-static void launch_dma(GemmParams p, int splits, hipStream_t stream) {
-  const int total_kt = (p.K + BK - 1) / BK;
-  p.ktiles_per_split = (total_kt + splits - 1) / splits;
-  splits = (total_kt + p.ktiles_per_split - 1) / p.ktiles_per_split;
-  const int tiles = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
-  constexpr int stage = BM * 128 + BN * 128;
-  constexpr int threads = 64 * WM * WN;
-  if constexpr (3 * stage > 160 * 1024) {  // 256x192: 2-stage ring (explicitly instantiated below)
-    hipLaunchKernelGGL((gemm_dma_kernel<BM, BN, WM, WN, AT, BT, EPI, 2>), dim3(tiles, 1, splits), dim3(threads),
-                       2 * stage, stream, p);
-  } else {
-    if (dma_ring_stages(BM, BN, tiles * splits, p.ktiles_per_split) == 3)
-      hipLaunchKernelGGL((gemm_dma_kernel<BM, BN, WM, WN, AT, BT, EPI, 3>), dim3(tiles, 1, splits), dim3(threads),
-                         3 * stage, stream, p);
-    else
-      hipLaunchKernelGGL((gemm_dma_kernel<BM, BN, WM, WN, AT, BT, EPI, 4>), dim3(tiles, 1, splits), dim3(threads),
-                         4 * stage, stream, p);
-  }
-}
-
-template <int BM, int BN, int WM, int WN, bool AT, bool BT, int EPI>
-static void launch_cfg(GemmParams p, int splits, hipStream_t stream) {
-  using SA = Stage<BM, AT>;
-  using SB = Stage<BN, BT>;
-  const int lds = 2 * (SA::BYTES + SB::BYTES);
-  const int total_kt = (p.K + BK - 1) / BK;
-  p.ktiles_per_split = (total_kt + splits - 1) / splits;
-  splits = (total_kt + p.ktiles_per_split - 1) / p.ktiles_per_split;
-  const int tiles = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
-  dim3 grid(tiles, 1, splits);
-  hipLaunchKernelGGL((gemm_kernel<BM, BN, WM, WN, AT, BT, EPI>), grid, dim3(256), lds, stream, p);
-}
-
-// (tag dispatch instead of `if constexpr`: hipcc 7.2 silently drops the host
-// stub of a kernel template first referenced inside an if-constexpr branch)
-// tile configs: 0 = 32x64, 1 = 64x64, 2 = 128x64, 3 = 128x128 (4 waves, 2x2);
-// 4 = 256x128, 5 = 128x128, 6 = 256x192 (8 waves, 4x2: 512-thread workgroups, for M >= BIG_M)
-constexpr int CFG_W8_256 = 4, CFG_W8_128 = 5, CFG_W8_192 = 6;
-// epilogues with no 4-wave workgroup reduction (HEAD / HEADL sum loss partials over 4 waves)
-constexpr bool wide8_epi(int epi) {
-  return epi == EPI_BF16 || epi == EPI_F32 || epi == EPI_QKV || epi == EPI_RESID || epi == EPI_GELU ||
-         epi == EPI_EMBED || epi == EPI_DGELU;
-}
-// ... and those the 256x192 tile is built for (plain operands only)
-constexpr bool big192_epi(bool bt, int epi) { return !bt && (epi == EPI_BF16 || epi == EPI_QKV || epi == EPI_GELU); }
-template <int EPI>
-struct Wide8 {
-  static constexpr bool value = wide8_epi(EPI);
-};
-template <bool AT, bool BT, int EPI, bool OK = EPI != EPI_DGELU>
-struct Big256 {
-  static void go(GemmParams p, int splits, hipStream_t stream) { launch_dma<256, 128, 4, 2, AT, BT, EPI>(p, splits, stream); }
-};
-template <bool AT, bool BT, int EPI>
-struct Big256<AT, BT, EPI, false> {
-  static void go(GemmParams, int, hipStream_t) {}
-};
-template <bool AT, bool BT, int EPI, bool OK = big192_epi(BT, EPI)>
-struct Big192 {  // 256x192 tiles, 2-stage ring (57 KiB per stage): N = 1152 in 6 column tiles
-  static void go(GemmParams p, int splits, hipStream_t stream) { launch_dma<256, 192, 4, 2, AT, BT, EPI>(p, splits, stream); }
-};
-template <bool AT, bool BT, int EPI>
-struct Big192<AT, BT, EPI, false> {  // not built for this epilogue: the 256-row config
-  static void go(GemmParams p, int splits, hipStream_t stream) {
-    if (EPI != EPI_DGELU) Big256<AT, BT, EPI>::go(p, splits, stream);
-    else launch_dma<128, 128, 4, 2, AT, BT, EPI>(p, splits, stream);
-  }
-};
-template <bool AT, bool BT, int EPI, bool OK = Wide8<EPI>::value>
-struct Launch8 {
-  static void go(GemmParams p, int splits, hipStream_t stream, int cfg) {
-    if (cfg == CFG_W8_192) { Big192<AT, BT, EPI>::go(p, splits, stream); return; }
-    // DGELU at 256x128 spills (88 B/lane of scratch): its 256-row config is the 128-row one
-    if (cfg == CFG_W8_256 && EPI != EPI_DGELU) Big256<AT, BT, EPI>::go(p, splits, stream);
-    else launch_dma<128, 128, 4, 2, AT, BT, EPI>(p, splits, stream);
-  }
-};
-template <bool AT, bool BT, int EPI>
-struct Launch8<AT, BT, EPI, false> {
-  static void go(GemmParams, int, hipStream_t, int) {
-    throw std::runtime_error("gemm: 8-wave tiles are not built for this epilogue");
-  }
-};
-template <bool AT, bool BT, int EPI>
-struct DmaTiles {
-  static void launch(GemmParams p, int splits, hipStream_t stream, int cfg) {
-    switch (cfg) {
-      case 0: launch_dma<32, 64, 2, 2, AT, BT, EPI>(p, splits, stream); break;
-      case 1: launch_dma<64, 64, 2, 2, AT, BT, EPI>(p, splits, stream); break;
-      case 2: launch_dma<128, 64, 2, 2, AT, BT, EPI>(p, splits, stream); break;
-      case 3: launch_dma<128, 128, 2, 2, AT, BT, EPI>(p, splits, stream); break;
-      default: Launch8<AT, BT, EPI>::go(p, splits, stream, cfg); break;
-    }
-  }
-};
-template <int EPI>
-struct DmaTiles<false, true, EPI> {  // transposed B (dgrad): BN = 64 (4 waves) or 128 (8 waves)
-  static void launch(GemmParams p, int splits, hipStream_t stream, int cfg) {
-    switch (cfg) {
-      case 0: launch_dma<32, 64, 2, 2, false, true, EPI>(p, splits, stream); break;
-      case 1: launch_dma<64, 64, 2, 2, false, true, EPI>(p, splits, stream); break;
-      case 2: case 3: launch_dma<128, 64, 2, 2, false, true, EPI>(p, splits, stream); break;
-      default: Launch8<false, true, EPI>::go(p, splits, stream, cfg); break;
-    }
-  }
-};
-template <bool BT, int EPI>
-struct DmaTiles<true, BT, EPI> {  // transposed A (wgrad): 64x64
-  static void launch(GemmParams p, int splits, hipStream_t stream, int) {
-    launch_dma<64, 64, 2, 2, true, BT, EPI>(p, splits, stream);
-  }
-};
-
-// Tile choice.  M < BIG_M (ViT-tiny / sampler shapes, M = 2-4k): 64x64 when that
-// alone gives ~1 workgroup per CU, else 32x64.  A cost model "operand bytes per CU"
-// that picked 128x64 / 128x128 for the big shapes of those sizes measured SLOWER
-// everywhere (qkv 2080x1152x384: 11.9 us at 128x128 vs 7.5 at 64x64; train step
-// -10%): more, smaller workgroups hide latency better than fewer bytes help, and was
-// removed.  M >= BIG_M (vit_small_200: M = 20,032): 8-wave 256x128 tiles (4x the
-// MFMA work per operand byte of 64x64, one 144 KiB 3-stage ring per CU), for the
-// epilogues that support them (Wide8).  gemm_set_tile_override() forces a config
-// (tests and micro-benchmarks).  The LDS-DMA ring needs K % 64 == 0 for
-// k-contiguous operands (transposed operands get zero rows past K from the buffer
-// bounds check).
-constexpr int BIG_M = 16384;
+// gemm_set_tile_override() forces a tile config (tests and micro-benchmarks)
 static std::atomic<int> g_tile_override{-1};
-static int pick_tiles(int M, int N, int K, int splits, bool at, bool bt, bool wide8, bool qkv = false) {
-  if (at) return 1;
-  const int forced = g_tile_override.load(std::memory_order_relaxed);
-  if (forced >= 0) return bt && forced == 3 ? 2 : forced;
-  // 8-wave 256x128 tiles only when they still give about one tile per CU: the
-  // oxford_flower sampler's N = 256 GEMMs (M = 16,448: 130 such tiles) run faster on
-  // 64x64 / 32x64 tiles (tools/ub_gemm_large.py 16448 .. 256: residual 19.7 vs 15.9 us,
-  // GELU 16.0 vs 13.2; vit_small_200 N = 384 at M = 20,032: 237 tiles, 8-wave faster)
-  // the QKV projection (N = 3D = 1,152 at vit_small_200): 256x192 tiles, 2-stage ring --
-  // 474 workgroups (1.85 rounds of 256 CUs) instead of 711 (2.8 rounds): 489 -> 453 us of
-  // QKV per step (profiles/qkv192_r6.txt)
-  if (wide8 && M >= BIG_M && ((M + 255) / 256) * ((N + 127) / 128) >= 236)
-    return qkv && N % 192 == 0 ? CFG_W8_192 : CFG_W8_256;
-  return ((M + 63) / 64) * ((N + 63) / 64) * splits >= 240 ? 1 : 0;
-}
 
-// The LDS-DMA path's tile config for an epilogue (launch_auto launches it,
-// gemm_dma_plan reports it).
-static int dma_cfg(int epi, bool at, bool bt, int M, int N, int K, int splits) {
-  // DGELU (input gradient through GELU + dropout, bf16 out) stays on 4-wave tiles at
-  // every measured M (M = 20,032: 25.5 vs 26.5 us; 40,064: 42.1 vs 49.9)
-  int cfg = pick_tiles(M, N, K, splits, at, bt, wide8_epi(epi) && epi != EPI_DGELU, epi == EPI_QKV);
-  // the GELU epilogue (erf-GELU + dropout per element, two bf16 outputs) is the
-  // heaviest in vector instructions: twice the waves of 32x64 tiles pay off on the
-  // sampler shape (M=4160: 6.56 vs 7.14 us, tools/gpu_tile_sweep3.sh); the other
-  // epilogues keep 64x64 there (QKV 11.45 vs 13.54, residual 6.65 vs 7.02)
-  // the patch embedding likewise (sampler M=4,096: 7.83 vs 9.08 us, tools/ub_sampler_ends.py)
-  if ((epi == EPI_GELU || epi == EPI_EMBED) && cfg == 1 && g_tile_override.load(std::memory_order_relaxed) < 0 &&
-      ((M + 31) / 32) * ((N + 63) / 64) <= 1024)
-    cfg = 0;
-  return cfg;
-}
-// the non-DMA GEMM (K % 64 != 0) takes 64x64 tiles from here, 32x64 below; no override
-static bool plain_big(int M, int N, int splits, bool at) {
-  return ((M + 63) / 64) * ((N + 63) / 64) * splits >= 240 || at;
-}
-
-template <bool AT, bool BT, int EPI>
-static void launch_auto(GemmParams p, int splits, hipStream_t stream) {
-  const bool dma_ok = AT || p.K % 64 == 0;
-  if (dma_ok) {
-    DmaTiles<AT, BT, EPI>::launch(p, splits, stream, dma_cfg(EPI, AT, BT, p.M, p.N, p.K, splits));
+// Launch what the plan names: the instantiation whose (BM, BN, waves, stages) equals it.
+static void launch_plan(const GemmPlan& pl, bool at, bool bt, int epi, GemmParams p, hipStream_t stream) {
+  p.ktiles_per_split = pl.ktiles_per_split;
+  const dim3 grid(pl.tiles, 1, pl.splits), block(64 * pl.waves);
+  const int key = kernel_key(at, bt, epi, pl.bm, pl.bn, pl.waves, pl.stages);
+  if (pl.dma) {
+    const int lds = pl.stages * gemm_stage_bytes(pl.bm, pl.bn);
+    switch (key) {
+#define DC_LAUNCH(AT, BT, EPI, BM, BN, WM, WN, S)                                                         \
+  case kernel_key(AT, BT, EPI, BM, BN, WM * WN, S):                                                       \
+    hipLaunchKernelGGL((gemm_dma_kernel<BM, BN, WM, WN, AT, BT, EPI, S>), grid, block, lds, stream, p); \
     return;
+      DC_RING_KERNELS(DC_LAUNCH)
+#undef DC_LAUNCH
+    }
+  } else {
+    switch (key) {
+#define DC_LAUNCH_TILE(BM, AT, BT, EPI)                                                     \
+  case kernel_key(AT, BT, EPI, BM, 64, 4, 2):                                               \
+    hipLaunchKernelGGL((gemm_kernel<BM, 64, 2, 2, AT, BT, EPI>), grid, block,               \
+                       2 * (Stage<BM, AT>::BYTES + Stage<64, BT>::BYTES), stream, p);       \
+    return;
+#define DC_LAUNCH(AT, BT, EPI) DC_LAUNCH_TILE(32, AT, BT, EPI) DC_LAUNCH_TILE(64, AT, BT, EPI)
+      DC_FAMILIES(DC_LAUNCH)
+#undef DC_LAUNCH
+#undef DC_LAUNCH_TILE
+    }
   }
-  if (plain_big(p.M, p.N, splits, AT)) launch_cfg<64, 64, 2, 2, AT, BT, EPI>(p, splits, stream);
-  else launch_cfg<32, 64, 2, 2, AT, BT, EPI>(p, splits, stream);
+  throw std::logic_error("gemm: the plan names a kernel that is not instantiated");
 }
-
-// Explicit instantiations: hipcc 7.2 intermittently fails to emit host launch
-// stubs for implicitly instantiated kernel templates (undefined
-// __device_stub__ at dlopen); build.py also checks the .so for that.
-#define DC_INST_DMAT(BM, BN, AT, BT, EPI)                                               \
-  template __global__ void gemm_dma_kernel<BM, BN, 2, 2, AT, BT, EPI, 4>(GemmParams); \
-  template __global__ void gemm_dma_kernel<BM, BN, 2, 2, AT, BT, EPI, 3>(GemmParams);
-#define DC_INST_DMA(BM, AT, BT, EPI) DC_INST_DMAT(BM, 64, AT, BT, EPI)
-#define DC_INST_DMA2(AT, BT, EPI) \
-  DC_INST_DMA(64, AT, BT, EPI) DC_INST_DMA(32, AT, BT, EPI) DC_INST_DMA(128, AT, BT, EPI)
-#define DC_INST_DMA3(EPI) DC_INST_DMA2(false, false, EPI) DC_INST_DMAT(128, 128, false, false, EPI)
-// 8-wave tiles (4x2 waves): 256x128 and 128x128
-#define DC_INST_W8(AT, BT, EPI)                                                    \
-  template __global__ void gemm_dma_kernel<256, 128, 4, 2, AT, BT, EPI, 3>(GemmParams); \
-  template __global__ void gemm_dma_kernel<256, 128, 4, 2, AT, BT, EPI, 4>(GemmParams); \
-  template __global__ void gemm_dma_kernel<128, 128, 4, 2, AT, BT, EPI, 3>(GemmParams); \
-  template __global__ void gemm_dma_kernel<128, 128, 4, 2, AT, BT, EPI, 4>(GemmParams);
-#define DC_INST_W192(EPI) template __global__ void gemm_dma_kernel<256, 192, 4, 2, false, false, EPI, 2>(GemmParams);
-DC_INST_W192(EPI_BF16) DC_INST_W192(EPI_QKV) DC_INST_W192(EPI_GELU)
-DC_INST_DMA3(EPI_BF16) DC_INST_W8(false, false, EPI_BF16)
-DC_INST_DMA3(EPI_F32) DC_INST_W8(false, false, EPI_F32)
-DC_INST_DMA3(EPI_QKV) DC_INST_W8(false, false, EPI_QKV)
-DC_INST_DMA3(EPI_RESID) DC_INST_W8(false, false, EPI_RESID)
-DC_INST_DMA3(EPI_GELU) DC_INST_W8(false, false, EPI_GELU)
-DC_INST_DMA3(EPI_HEAD)
-DC_INST_DMA3(EPI_EMBED) DC_INST_W8(false, false, EPI_EMBED)
-DC_INST_DMA3(EPI_HEADR)
-DC_INST_DMA3(EPI_HEADL)
-DC_INST_DMA3(EPI_HEADRS)
-DC_INST_DMA2(false, true, EPI_BF16) DC_INST_W8(false, true, EPI_BF16)
-DC_INST_DMA2(false, true, EPI_F32) DC_INST_W8(false, true, EPI_F32)
-DC_INST_DMA2(false, true, EPI_DGELU)
-DC_INST_DMA3(EPI_DGELU)  // the same on the k-contiguous path (transposed weight shadow)
-template __global__ void gemm_dma_kernel<128, 128, 4, 2, false, false, EPI_DGELU, 3>(GemmParams);
-template __global__ void gemm_dma_kernel<128, 128, 4, 2, false, false, EPI_DGELU, 4>(GemmParams);
-template __global__ void gemm_dma_kernel<128, 128, 4, 2, false, true, EPI_DGELU, 3>(GemmParams);
-template __global__ void gemm_dma_kernel<128, 128, 4, 2, false, true, EPI_DGELU, 4>(GemmParams);
-DC_INST_DMA(64, true, true, EPI_ATOMIC)
+static void launch_auto(bool at, bool bt, int epi, const GemmParams& p, int splits, hipStream_t stream) {
+  launch_plan(gemm_dma_plan(epi, at, bt, p.M, p.N, p.K, splits), at, bt, epi, p, stream);
+}
 
 // Whole-backward weight gradient: every dW += dy^T x of a training step (all
 // blocks, head, patch embedding; up to WM_MAX problems) in ONE launch after the
@@ -859,7 +732,7 @@ using namespace dc;
 static std::atomic<uint32_t*> g_stamps{nullptr};
 uint32_t* gemm_set_stamps(uint32_t* buf) { return g_stamps.exchange(buf); }
 
-static GemmParams base_params(const GemmArgs& a) {
+GemmParams dc::gemm_params_from_args(const GemmArgs& a) {
   GemmParams p{};
   p.stamps = g_stamps.load(std::memory_order_relaxed);
   p.A = reinterpret_cast<const bf16*>(a.A);
@@ -892,11 +765,6 @@ static GemmParams base_params(const GemmArgs& a) {
   return p;
 }
 
-GemmParams dc::gemm_params_from_args(const GemmArgs& a) {
-  GemmParams p = base_params(a);
-  return p;
-}
-
 static void check_vec(const GemmParams& p, int epi) {
   // the vector epilogue stores 4 consecutive output columns per lane
   if (epi != EPI_HEAD && (p.N % 4 != 0 || (epi == EPI_QKV && p.hd % 4 != 0) || (epi == EPI_EMBED && p.emb_dim % 4 != 0)))
@@ -909,76 +777,21 @@ static void check_vec(const GemmParams& p, int epi) {
 }
 
 void gemm_nt(const GemmArgs& a, int epi, hipStream_t stream) {
-  GemmParams p = base_params(a);
+  GemmParams p = gemm_params_from_args(a);
   check_vec(p, epi);
-  switch (epi) {
-    case EPI_BF16: launch_auto<false, false, EPI_BF16>(p, 1, stream); break;
-    case EPI_F32: launch_auto<false, false, EPI_F32>(p, 1, stream); break;
-    case EPI_QKV: launch_auto<false, false, EPI_QKV>(p, 1, stream); break;
-    case EPI_RESID: launch_auto<false, false, EPI_RESID>(p, 1, stream); break;
-    case EPI_GELU: launch_auto<false, false, EPI_GELU>(p, 1, stream); break;
-    case EPI_HEAD: launch_auto<false, false, EPI_HEAD>(p, 1, stream); break;
-    case EPI_EMBED: launch_auto<false, false, EPI_EMBED>(p, 1, stream); break;
-    case EPI_DGELU: launch_auto<false, false, EPI_DGELU>(p, 1, stream); break;  // dgrad through GELU, W^T given
-    case EPI_HEADR:
-      if (p.K % 64 != 0) throw std::runtime_error("gemm_nt: EPI_HEADR needs the LDS-DMA GEMM");
-      launch_auto<false, false, EPI_HEADR>(p, 1, stream);
-      break;
-    case EPI_HEADL:
-      if (p.K % 64 != 0) throw std::runtime_error("gemm_nt: EPI_HEADL needs the LDS-DMA GEMM");
-      launch_auto<false, false, EPI_HEADL>(p, 1, stream);
-      break;
-    case EPI_HEADRS:
-      if (p.K % 64 != 0) throw std::runtime_error("gemm_nt: EPI_HEADRS needs the LDS-DMA GEMM");
-      if ((p.head_mode != 5 && p.head_mode != 6) || p.rng == nullptr || p.coef == nullptr || p.res == nullptr ||
-          p.C2 == nullptr)
-        throw std::runtime_error("gemm_nt: EPI_HEADRS needs head mode 5 or 6 with rng, coef, x_t and x0_out");
-      launch_auto<false, false, EPI_HEADRS>(p, 1, stream);
-      break;
-    default: throw std::runtime_error("gemm_nt: unsupported epilogue");
-  }
+  if (epi == EPI_HEADRS && ((p.head_mode != 5 && p.head_mode != 6) || p.rng == nullptr || p.coef == nullptr ||
+                            p.res == nullptr || p.C2 == nullptr))
+    throw std::runtime_error("gemm_nt: EPI_HEADRS needs head mode 5 or 6 with rng, coef, x_t and x0_out");
+  launch_auto(false, false, epi, p, 1, stream);
 }
 
-// What launch_auto<at, bt, epi> would launch for an [M x N x K] problem in `splits` K
-// slices -- the tile after the fallbacks of DmaTiles / Launch8 / Big192 / Big256 and the
-// ring depth -- without launching anything.
 GemmPlan gemm_dma_plan(int epi, bool at, bool bt, int M, int N, int K, int splits) {
-  if (M < 1 || N < 1 || K < 1 || splits < 1) throw std::runtime_error("gemm_dma_plan: M, N, K, splits >= 1");
-  GemmPlan pl{};
-  const int total_kt = (K + BK - 1) / BK;
-  const int kps = (total_kt + splits - 1) / splits;
-  const int nsplit = (total_kt + kps - 1) / kps;
-  pl.dma = at || K % 64 == 0;
-  pl.waves = 4;
-  if (!pl.dma) {
-    pl.bm = plain_big(M, N, splits, at) ? 64 : 32;
-    pl.bn = 64;
-    pl.stages = 2;  // gemm_kernel double-buffers
-    return pl;
-  }
-  const int cfg = dma_cfg(epi, at, bt, M, N, K, splits);
-  if (at) { pl.bm = 64; pl.bn = 64; }                                // DmaTiles<true, BT>
-  else if (cfg == 0) { pl.bm = 32; pl.bn = 64; }
-  else if (cfg == 1) { pl.bm = 64; pl.bn = 64; }
-  else if (cfg == 2 || (cfg == 3 && bt)) { pl.bm = 128; pl.bn = 64; }  // DmaTiles<false, true>: BN = 64
-  else if (cfg == 3) { pl.bm = 128; pl.bn = 128; }
-  else {                                                             // Launch8
-    if (!wide8_epi(epi)) throw std::runtime_error("gemm: 8-wave tiles are not built for this epilogue");
-    pl.waves = 8;
-    pl.bm = 128; pl.bn = 128;
-    if (epi != EPI_DGELU) {
-      if (cfg == CFG_W8_192) { pl.bm = 256; pl.bn = big192_epi(bt, epi) ? 192 : 128; }
-      else if (cfg == CFG_W8_256) pl.bm = 256;
-    }
-  }
-  pl.stages = dma_ring_stages(pl.bm, pl.bn, ((M + pl.bm - 1) / pl.bm) * ((N + pl.bn - 1) / pl.bn) * nsplit, kps);
-  return pl;
+  return gemm_plan(epi, at, bt, M, N, K, splits, g_tile_override.load(std::memory_order_relaxed));
 }
 
 int gemm_nt_grid(int M, int N, int K) {
   // the epilogues that size a per-workgroup buffer from it (HEAD / HEADL: never 8-wave tiles)
-  const GemmPlan pl = gemm_dma_plan(EPI_HEAD, false, false, M, N, K, 1);
-  return ((M + pl.bm - 1) / pl.bm) * ((N + pl.bn - 1) / pl.bn);
+  return gemm_dma_plan(EPI_HEAD, false, false, M, N, K, 1).tiles;
 }
 
 int gemm_set_tile_override(int cfg) {
@@ -987,30 +800,28 @@ int gemm_set_tile_override(int cfg) {
 }
 
 void gemm_dgrad(const GemmArgs& a, int epi, hipStream_t stream) {
-  GemmParams p = base_params(a);
+  GemmParams p = gemm_params_from_args(a);
   check_vec(p, epi);
   switch (epi) {
     case EPI_BF16:
     case EPI_F32: {
-      // K split: slice z writes its partial product to C + z * split_stride
-      // (every slice non-empty; the consumer sums the slices)
-      const int kt = (p.K + 63) / 64;
-      const int splits = std::max(1, std::min(a.splits, kt));
-      if (splits != a.splits && a.splits > 1) throw std::runtime_error("gemm_dgrad: more K slices than k-tiles");
-      if (splits > 1 && (p.bias || (kt + splits - 1) / splits * (splits - 1) >= kt))
-        throw std::runtime_error("gemm_dgrad: K split needs no bias and a non-empty last slice");
-      if (epi == EPI_BF16) launch_auto<false, true, EPI_BF16>(p, splits, stream);
-      else launch_auto<false, true, EPI_F32>(p, splits, stream);
+      // K split: slice z writes its partial product to C + z * split_stride (the consumer
+      // sums the slices): as many slices as asked for, none empty, and no bias
+      const int splits = std::max(1, a.splits);
+      const GemmPlan pl = gemm_dma_plan(epi, false, true, p.M, p.N, p.K, splits);
+      if (splits > 1 && (p.bias || pl.splits != splits))
+        throw std::runtime_error("gemm_dgrad: K split needs no bias and a non-empty k-tile range for every slice");
+      launch_plan(pl, false, true, epi, p, stream);
     } break;
-    case EPI_DGELU: launch_auto<false, true, EPI_DGELU>(p, 1, stream); break;
+    case EPI_DGELU: launch_auto(false, true, epi, p, 1, stream); break;
     default: throw std::runtime_error("gemm_dgrad: unsupported epilogue");
   }
 }
 
 void gemm_wgrad(const GemmArgs& a, int splits, hipStream_t stream) {
-  GemmParams p = base_params(a);
+  GemmParams p = gemm_params_from_args(a);
   check_vec(p, EPI_ATOMIC);
-  launch_auto<true, true, EPI_ATOMIC>(p, splits, stream);
+  launch_auto(true, true, EPI_ATOMIC, p, splits, stream);
 }
 
 int wgrad_embed_workgroups(const WgradEmbed& emb, bool wide) {

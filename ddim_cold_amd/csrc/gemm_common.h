@@ -4,10 +4,12 @@
 // counted vmcnt waits, raw barriers and the XCD-aware block remap.
 #pragma once
 #include "common.h"
+#include "gemm_plan.h"
 
 namespace dc {
 
 constexpr int BK = 64;
+static_assert(BK == GEMM_BK, "the kernels' k-tile depth is the plan's");
 
 __device__ __forceinline__ int swz(int r) { return (r >> 1) & 7; }
 

@@ -71,7 +71,7 @@ struct GemmParams {
   uint32_t* stamps;    // phase profiling (gemm_set_stamps): per workgroup GEMM_STAMP_WORDS words
 };
 
-// the kernel parameter block of a host GemmArgs (gemm.hip base_params)
+// the kernel parameter block of a host GemmArgs (gemm.hip; the one builder every entry point uses)
 GemmParams gemm_params_from_args(const GemmArgs& a);
 
 // Phase stamps of the LDS-DMA GEMM (tools/ub_gemm_stamps.py): s_memrealtime (100 MHz)

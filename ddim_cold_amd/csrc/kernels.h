@@ -4,26 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdexcept>
+#include "gemm_plan.h"
 #include "wgrad_plan.h"
-
-enum GemmEpi : int {
-  EPI_BF16 = 0,    // C bf16 = acc (+bias)
-  EPI_F32 = 1,     // C f32 = acc (+bias)
-  EPI_QKV = 2,     // +bias, scatter to head-major [3,B,H,N,hd] bf16
-  EPI_RESID = 3,   // C f32 = res + DropPath(Dropout(acc+bias))
-  EPI_GELU = 4,    // C = u = acc+bias (bf16) ; C2 = h = Dropout(GELU(u)) (bf16)
-  EPI_HEAD = 5,    // +bias, unpatchify token rows into a [B,C,H,W] f32 image
-  EPI_EMBED = 6,   // patch rows -> token rows: +bias +pos +temb[t], Dropout, f32
-  EPI_DGELU = 7,   // C bf16 = Dropout(acc) * GELU'(aux)
-  EPI_ATOMIC = 8,  // C f32 += acc (split-K / gradient accumulate) ; bias -> fused column sum
-  EPI_ACC = 9,     // C f32 += acc, one writer per element (no split) ; bias likewise
-  EPI_HEADR = 10,  // sampler step on patch rows: +bias, clamp (+DDIM update), f32 [B*P][C*p*p]
-                   //   in head-output column order (contiguous: vector epilogue)
-  EPI_HEADL = 11,  // training loss on patch rows: smooth-L1 vs a [B*P][C*p*p] target (head order),
-                   //   token-layout bf16 gradient, one loss partial per workgroup
-  EPI_HEADRS = 12, // EPI_HEADR's DDIM update with noise (eta > 0): x_next += sigma z, z drawn in the
-                   //   epilogue (randn_kernel's element at the destination index; rng, site_drop = site)
-};
 
 struct GemmArgs {
   const void* A = nullptr;
@@ -80,19 +62,13 @@ struct GemmArgs {
 void gemm_nt(const GemmArgs& a, int epi, hipStream_t stream);
 // workgroups gemm_nt launches for an [M x N x K] problem (one split)
 int gemm_nt_grid(int M, int N, int K);
-// host-only query: the kernel gemm_nt (at = bt = false), gemm_dgrad (bt) or gemm_wgrad
-// (at, bt) would launch for this epilogue and problem under the current tile override --
-// LDS-DMA ring or the plain K % 64 != 0 kernel, the tile after every fallback (e.g.
-// config 3 -> 128x64 for transposed B, DGELU 256 -> 128 rows), waves per workgroup and
-// ring depth.  Launches nothing.  Throws where the launch would (8-wave override on an
-// epilogue that is not built for it).
-struct GemmPlan {
-  bool dma = false;
-  int bm = 0, bn = 0, waves = 0, stages = 0;
-};
+// host-only query: gemm_plan (gemm_plan.h) under the current tile override -- the kernel
+// gemm_nt (at = bt = false), gemm_dgrad (bt) or gemm_wgrad (at, bt) launches for this
+// epilogue and problem, with its K split and grid.  The launches call the same function, so
+// this throws exactly where they would.  Launches nothing.
 GemmPlan gemm_dma_plan(int epi, bool at, bool bt, int M, int N, int K, int splits);
 // force a GEMM tile config for every later launch (-1 = automatic choice; 0..6, see
-// gemm.hip "tile configs"); returns the previous setting.  Tests / micro-benchmarks.
+// gemm_plan.h "tile configs"); returns the previous setting.  Tests / micro-benchmarks.
 int gemm_set_tile_override(int cfg);
 // phase stamps of every later LDS-DMA GEMM launch (GEMM_STAMP_WORDS words per
 // workgroup, gemm_epi.h) into buf; nullptr turns them off.  Returns the previous buffer.

@@ -122,11 +122,15 @@ def qkv_fwd(a, w, b, B: int, N: int, H: int, fold=None):
 
 class gemm_tile:
     """Context manager forcing the GEMM tile config of every launch inside it
-    (csrc/gemm.hip: 0 = 32x64, 1 = 64x64, 2 = 128x64, 3 = 128x128 with 4 waves;
+    (csrc/gemm_plan.h: 0 = 32x64, 1 = 64x64, 2 = 128x64, 3 = 128x128 with 4 waves;
     4 = 256x128, 5 = 128x128, 6 = 256x192 with 8 waves; -1 = automatic).  Config 6 is
     built for the plain-operand BF16 / QKV / GELU epilogues only: elsewhere it runs as
-    256x128 (128x128 for the GELU input gradient); ``torch.ops.ddim_cold.gemm_plan``
-    tells which tile and ring depth a launch takes.  Tests and micro-benchmarks; the
+    256x128 (128x128 for the GELU input gradient); config 3 is 128x64 for transposed B
+    (``gemm_cfg_fallback``).  The launch follows ``gemm_plan`` of that header, and
+    ``torch.ops.ddim_cold.gemm_plan`` is the same function: it names the tile and ring
+    depth a launch takes and raises where the launch would (an 8-wave config on an
+    epilogue without 8-wave tiles, a sampler / loss head epilogue at K % 64 != 0, an
+    operand layout and epilogue without kernels).  Tests and micro-benchmarks; the
     automatic choice is the production path."""
 
     def __init__(self, cfg: int):

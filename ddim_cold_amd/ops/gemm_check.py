@@ -43,7 +43,7 @@ EXACT_LIMIT = float(1 << 24)  # fp32 holds every integer of magnitude <= 2^24
 EPI_BF16, EPI_F32, EPI_QKV, EPI_RESID, EPI_GELU, EPI_HEAD, EPI_EMBED, EPI_DGELU, EPI_ATOMIC = range(9)
 EPI_HEADR = 10
 
-# csrc/gemm.hip tile configs: cfg -> (BM, BN, waves)
+# csrc/gemm_plan.h tile configs (GEMM_TILES): cfg -> (BM, BN, waves)
 TILES = {0: (32, 64, 4), 1: (64, 64, 4), 2: (128, 64, 4), 3: (128, 128, 4),
          4: (256, 128, 8), 5: (128, 128, 8), 6: (256, 192, 8)}
 
@@ -114,7 +114,7 @@ FIXED_DEPTH_TILES = [(c, 2 if 3 * _stage_bytes(c) > 160 * 1024 else 3) for c in 
 
 def depth_shape(cfg: int) -> Tuple[int, int]:
     """(M, N) just over the co-residency threshold of tile ``cfg`` (256 x per_cu4
-    workgroups, csrc/gemm.hip dma_ring_stages): N = 1,024 and one row more than
+    workgroups, csrc/gemm_plan.h gemm_ring_stages): N = 1,024 and one row more than
     fills the last whole row tile under the threshold."""
     bm, bn, _ = TILES[cfg]
     per_cu4 = (160 * 1024) // (4 * (bm * 128 + bn * 128))

@@ -4,13 +4,19 @@ bit, over every tile configuration, ring depth, operand reader and edge.
 With small-integer bf16 operands every partial sum is an exact fp32 integer in any
 summation order, so the tolerance is zero; a position probe (one-hot rows against a
 coded operand) names the element each output was read from.  Every case asserts through
-``torch.ops.ddim_cold.gemm_plan`` that the (path, tile, ring depth) it names is the one
-that ran.  Caller-provided outputs sit in canaried buffers (writes past row M / column N).
+``torch.ops.ddim_cold.gemm_plan`` the (path, tile, ring depth) of its launch: the op is
+``gemm_plan`` of csrc/gemm_plan.h under the current override, the function every launch
+calls and follows (``launch_auto`` in gemm.hip launches the instantiation whose tile, waves
+and depth equal the plan, or fails), so the kernel it names is the one that ran.  The
+mirrors ``expected_tile`` / ``expected_stages`` below are the independent statement of
+the rule.  Caller-provided outputs sit in canaried buffers (writes past row M / column N).
 
 Tile configs (``ops.gemm_tile``): 0 = 32x64, 1 = 64x64, 2 = 128x64, 3 = 128x128 (4 waves);
 4 = 256x128, 5 = 128x128, 6 = 256x192 (8 waves).  Config 6 is built for the plain-operand
 BF16 / QKV / GELU epilogues and runs as 256x128 elsewhere (128x128 for DGELU); config 3 is
-128x64 for transposed B; DGELU's 256-row config is the 128-row one.  Ring depth: 256x192
+128x64 for transposed B; DGELU's 256-row config is the 128-row one (``gemm_cfg_fallback``
+in csrc/gemm_plan.h, the one place these are written; tests/cpp/gemm_plan_check.cpp checks
+them for every epilogue without a GPU).  Ring depth (``gemm_ring_stages``): 256x192
 always 2, 256x128 always 3, the others 3 when the grid exceeds 256 x per_cu4 workgroups
 with at most 8 k-tiles per slice, else 4.  ``linear_wgrad_multi`` has its own kernel and
 its own plan (csrc/wgrad_plan.h, ``torch.ops.ddim_cold.wgrad_multi_plan``): a 64x64 tile,

@@ -8,6 +8,11 @@
                                                      plain-operand BF16 / QKV / GELU epilogues,
                                                      the automatic choice for QKV with N % 192 == 0)
 
+Where a config is not built for a family the launch takes the tile ``gemm_cfg_fallback`` of
+csrc/gemm_plan.h names (6 -> 256x128 elsewhere, 4 -> 128x128 for DGELU, 3 -> 128x64 for
+transposed B): the launch follows that header's ``gemm_plan``, the same function
+``torch.ops.ddim_cold.gemm_plan`` reports.
+
 Shapes include the vit_small_200 training rows (M = 32 * 626 = 20,032, not a
 multiple of 256), ragged M / N, the K = 1,152 QKV input gradient, and the
 LayerNorm-fold consumer and producer epilogues.  Bit-exact integer probes of the same
