@@ -32,7 +32,7 @@ constexpr float LN2 = 0.6931471805599453f;
 
 template <int HD>
 struct AC {
-  static constexpr int S = 2 * HD + 32;   // LDS row stride in bytes
+  static constexpr int S = attn_row_stride(HD);  // LDS row stride in bytes (2 * HD + 32)
   static constexpr int TILE = 64 * S;     // one 64-row tile
   static constexpr int KS = HD / 32;      // MFMA k-steps over hd
   static constexpr int DT = HD / 16;      // 16-row tiles over hd
@@ -443,14 +443,6 @@ __global__ __launch_bounds__(256) void attn_fwd_flash2_kernel(const bf16* __rest
     }
   }
 }
-template __global__ void attn_fwd_flash2_kernel<32, true>(const bf16*, bf16*, float*, int, int, int, float,
-                                                          const int64_t*, int, uint32_t, float, uint32_t*);
-template __global__ void attn_fwd_flash2_kernel<32, false>(const bf16*, bf16*, float*, int, int, int, float,
-                                                           const int64_t*, int, uint32_t, float, uint32_t*);
-template __global__ void attn_fwd_flash2_kernel<64, true>(const bf16*, bf16*, float*, int, int, int, float,
-                                                          const int64_t*, int, uint32_t, float, uint32_t*);
-template __global__ void attn_fwd_flash2_kernel<64, false>(const bf16*, bf16*, float*, int, int, int, float,
-                                                           const int64_t*, int, uint32_t, float, uint32_t*);
 
 // ============================================================================ forward, medium sequences
 // Resident-KV forward (128 < N <= 320, e.g. the 257-token OxfordFlower config):
@@ -467,7 +459,7 @@ __global__ __launch_bounds__(640) void attn_fwd_resident_kernel(const bf16* __re
                                                                 uint32_t* __restrict__ keep) {
   using C = AC<HD>;
   extern __shared__ __attribute__((aligned(16))) char dyn[];
-  const int NP = (N + 63) / 64 * 64;  // keys padded to whole 64-key chunks
+  const int NP = (N + 63) / 64 * 64;  // keys padded to whole 64-key chunks (2 * NP * S bytes: attn_resident_lds)
   char* Kl = dyn;
   char* Vl = dyn + NP * C::S;
   const int bh = blockIdx.x, b = bh / H, h = bh - b * H;
@@ -586,43 +578,12 @@ __global__ __launch_bounds__(640) void attn_fwd_resident_kernel(const bf16* __re
     }
   }
 }
-template __global__ void attn_fwd_resident_kernel<32, true>(const bf16*, bf16*, float*, int, int, int, float,
-                                                            const int64_t*, int, uint32_t, float, uint32_t*);
-template __global__ void attn_fwd_resident_kernel<32, false>(const bf16*, bf16*, float*, int, int, int, float,
-                                                             const int64_t*, int, uint32_t, float, uint32_t*);
-template __global__ void attn_fwd_resident_kernel<64, true>(const bf16*, bf16*, float*, int, int, int, float,
-                                                            const int64_t*, int, uint32_t, float, uint32_t*);
-template __global__ void attn_fwd_resident_kernel<64, false>(const bf16*, bf16*, float*, int, int, int, float,
-                                                             const int64_t*, int, uint32_t, float, uint32_t*);
-
-template <int HD>
-static void launch_resident(const bf16* q, bf16* out, float* lse, int B, int H, int N, float scale,
-                            const int64_t* rng, int site, uint32_t thr, float dsc, hipStream_t stream,
-                            uint32_t* keep) {
-  const int waves = (N + 31) / 32;
-  const int NP = (N + 63) / 64 * 64;
-  const int lds = 2 * NP * AC<HD>::S;
-  static bool attr = [] {
-    bool ok = true;
-    for (const void* f : {reinterpret_cast<const void*>(&attn_fwd_resident_kernel<HD, true>),
-                          reinterpret_cast<const void*>(&attn_fwd_resident_kernel<HD, false>)})
-      ok = ok && hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess;
-    return ok;
-  }();
-  (void)attr;
-  if (thr)
-    hipLaunchKernelGGL((attn_fwd_resident_kernel<HD, true>), dim3(B * H), dim3(64 * waves), lds, stream, q, out, lse,
-                       B, H, N, scale, rng, site, thr, dsc, keep);
-  else
-    hipLaunchKernelGGL((attn_fwd_resident_kernel<HD, false>), dim3(B * H), dim3(64 * waves), lds, stream, q, out, lse,
-                       B, H, N, scale, rng, site, thr, dsc, nullptr);
-}
 
 // ============================================================================ backward: dQ (+delta)
 // U query groups of 16 per wave (64 U queries per workgroup): every K / V fragment a
 // wave reads from LDS feeds U MFMAs (S and dP of each group), and every K^T fragment of
-// the dQ update U more.  Only U = 1 is built (attn_bwd_launch: U = 2 measured slower,
-// it costs occupancy); the two 32-key halves of a tile each run S / dP -> dS -> dQ in
+// the dQ update U more.  Only U = 1 is built (U = 2 measured slower, it costs
+// occupancy: the numbers are at the kernel list); the two 32-key halves of a tile each run S / dP -> dS -> dQ in
 // turn, so only half a tile's dS is live (128 -> 114 VGPRs).
 template <int HD, int U, bool KB>
 __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const bf16* __restrict__ dout, const bf16* __restrict__ qkv,
@@ -1039,20 +1000,6 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const bf16* __restric
     }
   }
 }
-#define DC_INST_BWD(HD, U)                                                                                       \
-  template __global__ void attn_bwd_dq_kernel<HD, U, true>(const bf16*, const bf16*, const bf16*, const float*,   \
-                                                           float*, bf16*, int, int, int, float, const int64_t*,    \
-                                                           int, uint32_t, float, const uint32_t*);                 \
-  template __global__ void attn_bwd_dq_kernel<HD, U, false>(const bf16*, const bf16*, const bf16*, const float*,  \
-                                                            float*, bf16*, int, int, int, float, const int64_t*,   \
-                                                            int, uint32_t, float, const uint32_t*);                \
-  template __global__ void attn_bwd_dkv_kernel<HD, U, true>(const bf16*, const bf16*, const float*, const float*,  \
-                                                            bf16*, int, int, int, float, const int64_t*, int,      \
-                                                            uint32_t, float, const uint32_t*);                     \
-  template __global__ void attn_bwd_dkv_kernel<HD, U, false>(const bf16*, const bf16*, const float*, const float*, \
-                                                             bf16*, int, int, int, float, const int64_t*, int,     \
-                                                             uint32_t, float, const uint32_t*);
-DC_INST_BWD(32, 1) DC_INST_BWD(64, 1)
 
 // ============================================================================ short sequences (N <= 128)
 // One workgroup per (b, h) holding the WHOLE sequence: NP = 32*ceil(N/32) padded
@@ -1074,7 +1021,7 @@ struct ShortImg {
   static constexpr int NT = NP * 4;        // threads of the workgroup
   static constexpr int CPR = HD / 8;       // 16-B chunks per row
   static constexpr int PER = NP * CPR / NT;  // chunks per thread (= HD / 32)
-  static constexpr int RS = 2 * HD + 32;   // padded LDS row stride (bytes)
+  static constexpr int RS = attn_row_stride(HD);  // padded LDS row stride (bytes)
   u32x4 v[PER];
   // chunk c -> (row, 16-B chunk).  64-B rows (hd 32): an 8-lane ds_write_b128
   // group takes rows r and r+2 (48 dwords apart, disjoint banks mod 32) instead
@@ -1147,8 +1094,9 @@ __global__ __launch_bounds__(NP * 4) void attn_fwd_short_kernel(const bf16* __re
   using I = ShortImg<HD, NP>;
   constexpr int RS = I::RS, KS = HD / 32, DT = HD / 16, KT = NP / 16;
   static_assert(KT * 4 <= 32, "one 32-bit keep word per lane");
-  // dynamic LDS (2 * NP * RS bytes, see short_lds): with static LDS, 384-thread
+  // dynamic LDS (2 * NP * RS bytes, attn_short_fwd_lds): with static LDS, 384-thread
   // workgroups were admitted one per CU from ~60 KB on (tools/ub_lds_census.hip)
+  static_assert(2 * NP * RS == attn_short_fwd_lds(HD, NP), "K and V images vs the plan's LDS bytes");
   extern __shared__ __attribute__((aligned(16))) char lds[];
   char* Kl = lds;
   char* Vl = lds + NP * RS;
@@ -1249,11 +1197,12 @@ __global__ __launch_bounds__(NP * 4) void attn_bwd_short_kernel(const bf16* __re
                                                                 int site, uint32_t thr, float dsc,
                                                                 const uint32_t* __restrict__ keep_bits) {
   using I = ShortImg<HD, NP>;
-  constexpr int RS = I::RS, PS = 2 * NP + 32, KS = HD / 32, DT = HD / 16, KT = NP / 16;
-  // dynamic LDS (4 * NP * RS + 2 * NP * PS bytes, see short_lds): the same image as a
+  constexpr int RS = I::RS, PS = attn_short_pimg_stride(NP), KS = HD / 32, DT = HD / 16, KT = NP / 16;
+  // dynamic LDS (4 * NP * RS + 2 * NP * PS bytes, attn_short_bwd_lds): the same image as a
   // static array (79,872 B at NP 96) got ONE 384-thread workgroup per CU instead of two
   // -- 128 of the ViT-tiny step's 384 workgroups then waited for a second round
   // (workgroup-entry timestamps, tools/ub_lds_census.hip)
+  static_assert(4 * NP * RS + 2 * NP * PS == attn_short_bwd_lds(HD, NP), "the six images vs the plan's LDS bytes");
   extern __shared__ __attribute__((aligned(16))) char lds[];
   char* Ql = lds;
   char* Kl = Ql + NP * RS;
@@ -1390,185 +1339,143 @@ __global__ __launch_bounds__(NP * 4) void attn_bwd_short_kernel(const bf16* __re
   }
 }
 
-// LDS bytes of the short kernels' images (dynamic shared memory)
-template <int HD, int NP>
-struct ShortLds {
-  static constexpr int RS = ShortImg<HD, NP>::RS, PS = 2 * NP + 32;
-  static constexpr int FWD = 2 * NP * RS;
-  static constexpr int BWD = 4 * NP * RS + 2 * NP * PS;
-};
+// ============================================================================ kernel list
+// The kernels, listed once: the explicit instantiations and the launch switch below are
+// both generated from this list, and which kernel a problem gets is attn_plan's decision
+// alone (attn_plan.h).  Explicit instantiations at namespace scope for the reason given at
+// gemm.hip's list (hipcc's launch stubs of implicitly instantiated kernel templates).  Every
+// entry is checked against attn_kernel_built and their number against attn_kernels_built():
+// the list is the predicate's set, no more and no less.
+//   V1(HD)  FLASH2(HD, DROP)  RESIDENT(HD, DROP)  SHORT_FWD(HD, NP, DROP)  SHORT_BWD(HD, NP, DROP, KB)
+//   LONG_BWD(HD, KB): the dQ and the dK/dV kernel, one 16-row group per wave (U = 1).
+//     Measured slower and not built: U = 2 (every LDS fragment feeding two MFMAs; N=626 p=0.1
+//     stored masks 154.1 vs 146.1 us, N=2,501 448 vs 337: 174 / 236 VGPRs put dQ / dK-dV at
+//     2 waves per SIMD against 4 / 3), and a dK/dV prefetch two query tiles ahead in two
+//     register sets (178 VGPRs, 2 waves per SIMD: 180 vs 146 us) -- the kernels need the
+//     latency hiding of occupancy more
+#define DC_HD_FLAG(X) X(32, true) X(32, false) X(64, true) X(64, false)
+#define DC_NP4(X, HD, ...) X(HD, 32, __VA_ARGS__) X(HD, 64, __VA_ARGS__) X(HD, 96, __VA_ARGS__) X(HD, 128, __VA_ARGS__)
+#define DC_SHORT(X, ...) DC_NP4(X, 32, __VA_ARGS__) DC_NP4(X, 64, __VA_ARGS__)
+#define DC_ATTN_KERNELS(V1, FLASH2, RESIDENT, LONG_BWD, SHORT_FWD, SHORT_BWD)  \
+  V1(32) V1(64) DC_HD_FLAG(FLASH2) DC_HD_FLAG(RESIDENT) DC_HD_FLAG(LONG_BWD)    \
+  DC_SHORT(SHORT_FWD, true) DC_SHORT(SHORT_FWD, false)                          \
+  DC_SHORT(SHORT_BWD, true, true) DC_SHORT(SHORT_BWD, true, false) DC_SHORT(SHORT_BWD, false, false)
 
-template <typename K>
-static void allow_lds(K kernel, int bytes) {
-  if (bytes > 64 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-}
-
-template <int HD, int NP, bool DROP>
-struct ShortLaunch {
-  static void run(bool bwd, const bf16* d, const bf16* q, const bf16* o, float* lse, const float* lse_in,
-                  bf16* outp, int B, int H, int N, float scale, const int64_t* rng, int site, uint32_t thr,
-                  float dsc, hipStream_t stream, uint32_t* kb) {
-    using L = ShortLds<HD, NP>;
-    static const bool attr = [] {
-      allow_lds(&attn_fwd_short_kernel<HD, NP, DROP>, L::FWD);
-      allow_lds(&attn_bwd_short_kernel<HD, NP, DROP, false>, L::BWD);
-      allow_lds(&attn_bwd_short_kernel<HD, NP, DROP, DROP>, L::BWD);
-      return true;
-    }();
-    (void)attr;
-    if (!bwd)
-      hipLaunchKernelGGL((attn_fwd_short_kernel<HD, NP, DROP>), dim3(B * H), dim3(NP * 4), L::FWD, stream, q, outp,
-                         lse, B, H, N, scale, rng, site, thr, dsc, kb);
-    else if (DROP && kb != nullptr)  // stored drop flags: the KB instantiation
-      hipLaunchKernelGGL((attn_bwd_short_kernel<HD, NP, DROP, DROP>), dim3(B * H), dim3(NP * 4), L::BWD, stream, d,
-                         q, o, lse_in, outp, B, H, N, scale, rng, site, thr, dsc, kb);
-    else
-      hipLaunchKernelGGL((attn_bwd_short_kernel<HD, NP, DROP, false>), dim3(B * H), dim3(NP * 4), L::BWD, stream, d,
-                         q, o, lse_in, outp, B, H, N, scale, rng, site, thr, dsc, kb);
-  }
-};
-
-template <int HD, int NP>
-static void launch_short(bool bwd, const bf16* d, const bf16* q, const bf16* o, float* lse, const float* lse_in,
-                         bf16* outp, int B, int H, int N, float scale, const int64_t* rng, int site, uint32_t thr,
-                         float dsc, hipStream_t stream, uint32_t* kb) {
-  if (thr)
-    ShortLaunch<HD, NP, true>::run(bwd, d, q, o, lse, lse_in, outp, B, H, N, scale, rng, site, thr, dsc, stream, kb);
-  else
-    ShortLaunch<HD, NP, false>::run(bwd, d, q, o, lse, lse_in, outp, B, H, N, scale, rng, site, thr, dsc, stream, kb);
-}
-
-template <int HD>
-static void dispatch_short(bool bwd, const bf16* d, const bf16* q, const bf16* o, float* lse, const float* lse_in,
-                           bf16* outp, int B, int H, int N, float scale, const int64_t* rng, int site, uint32_t thr,
-                           float dsc, hipStream_t stream, uint32_t* kb = nullptr) {
-  switch ((N + 31) / 32) {
-    case 1: launch_short<HD, 32>(bwd, d, q, o, lse, lse_in, outp, B, H, N, scale, rng, site, thr, dsc, stream, kb); break;
-    case 2: launch_short<HD, 64>(bwd, d, q, o, lse, lse_in, outp, B, H, N, scale, rng, site, thr, dsc, stream, kb); break;
-    case 3: launch_short<HD, 96>(bwd, d, q, o, lse, lse_in, outp, B, H, N, scale, rng, site, thr, dsc, stream, kb); break;
-    default: launch_short<HD, 128>(bwd, d, q, o, lse, lse_in, outp, B, H, N, scale, rng, site, thr, dsc, stream, kb); break;
-  }
-}
-
-#define DC_INST_SHORT1(HD, NP, DR)                                                                                 \
-  template __global__ void attn_fwd_short_kernel<HD, NP, DR>(const bf16*, bf16*, float*, int, int, int, float,    \
-                                                             const int64_t*, int, uint32_t, float, uint32_t*);    \
-  template __global__ void attn_bwd_short_kernel<HD, NP, DR, false>(const bf16*, const bf16*, const bf16*,        \
-                                                                     const float*, bf16*, int, int, int, float,   \
-                                                                     const int64_t*, int, uint32_t, float,        \
-                                                                     const uint32_t*);
-#define DC_INST_SHORT(HD, NP)                                                                                      \
-  DC_INST_SHORT1(HD, NP, true) DC_INST_SHORT1(HD, NP, false)                                                       \
-  template __global__ void attn_bwd_short_kernel<HD, NP, true, true>(const bf16*, const bf16*, const bf16*,        \
-                                                                      const float*, bf16*, int, int, int, float,  \
-                                                                      const int64_t*, int, uint32_t, float,       \
-                                                                      const uint32_t*);
-DC_INST_SHORT(32, 32) DC_INST_SHORT(32, 64) DC_INST_SHORT(32, 96) DC_INST_SHORT(32, 128)
-DC_INST_SHORT(64, 32) DC_INST_SHORT(64, 64) DC_INST_SHORT(64, 96) DC_INST_SHORT(64, 128)
-
-
-constexpr int SHORT_MAX_N = 128;
+#define DC_FWD_SIG const bf16*, bf16*, float*, int, int, int, float, const int64_t*, int, uint32_t, float
+#define DC_BWD_SIG bf16*, int, int, int, float, const int64_t*, int, uint32_t, float, const uint32_t*
+#define DC_BUILT(K, HD, NP, DR, KB) \
+  static_assert(attn_kernel_built(AttnKernel::K, HD, NP, DR, KB), "a kernel outside attn_kernel_built");
+#define DC_INST_V1(HD) \
+  DC_BUILT(FWD_V1, HD, 0, false, false) template __global__ void attn_fwd_kernel<HD>(DC_FWD_SIG);
+#define DC_INST_FLASH2(HD, DR) \
+  DC_BUILT(FWD_FLASH2, HD, 0, DR, false) template __global__ void attn_fwd_flash2_kernel<HD, DR>(DC_FWD_SIG, uint32_t*);
+#define DC_INST_RESIDENT(HD, DR) \
+  DC_BUILT(FWD_RESIDENT, HD, 0, DR, false) template __global__ void attn_fwd_resident_kernel<HD, DR>(DC_FWD_SIG, uint32_t*);
+#define DC_INST_LONG_BWD(HD, KB)                                                                            \
+  DC_BUILT(BWD_DQ, HD, 0, false, KB) DC_BUILT(BWD_DKV, HD, 0, false, KB)                                    \
+  template __global__ void attn_bwd_dq_kernel<HD, 1, KB>(const bf16*, const bf16*, const bf16*, const float*, float*, DC_BWD_SIG); \
+  template __global__ void attn_bwd_dkv_kernel<HD, 1, KB>(const bf16*, const bf16*, const float*, const float*, DC_BWD_SIG);
+#define DC_INST_SHORT_FWD(HD, NP, DR) \
+  DC_BUILT(FWD_SHORT, HD, NP, DR, false) template __global__ void attn_fwd_short_kernel<HD, NP, DR>(DC_FWD_SIG, uint32_t*);
+#define DC_INST_SHORT_BWD(HD, NP, DR, KB) \
+  DC_BUILT(BWD_SHORT, HD, NP, DR, KB)     \
+  template __global__ void attn_bwd_short_kernel<HD, NP, DR, KB>(const bf16*, const bf16*, const bf16*, const float*, DC_BWD_SIG);
+#define DC_COUNT1(...) +1
+#define DC_COUNT2(...) +2
+DC_ATTN_KERNELS(DC_INST_V1, DC_INST_FLASH2, DC_INST_RESIDENT, DC_INST_LONG_BWD, DC_INST_SHORT_FWD, DC_INST_SHORT_BWD)
+static_assert(0 DC_ATTN_KERNELS(DC_COUNT1, DC_COUNT1, DC_COUNT1, DC_COUNT2, DC_COUNT1, DC_COUNT1) == attn_kernels_built(),
+              "a kernel of attn_kernel_built is not in the list");
+#undef DC_INST_V1
+#undef DC_INST_FLASH2
+#undef DC_INST_RESIDENT
+#undef DC_INST_LONG_BWD
+#undef DC_INST_SHORT_FWD
+#undef DC_INST_SHORT_BWD
+#undef DC_BUILT
+#undef DC_COUNT1
+#undef DC_COUNT2
+#undef DC_FWD_SIG
+#undef DC_BWD_SIG
 
 }  // namespace dc
 
+// ============================================================================ host API
 using namespace dc;
 
-// Long sequences: the flash / resident forwards store one 64-bit keep word per
-// (b, h, 64-key tile, query) for the backward (attn_fwd_launch picks them whenever
-// it is handed a keep buffer); short ones one 32-bit word per lane.
-static bool long_keep_path(int B, int H, int N) { return N >= 384 || (N <= 320 && B * H >= 192); }
-
-int64_t attn_keep_words(int B, int H, int N, int hd) {
-  if (hd != 32 && hd != 64) return 0;
-  if (N <= SHORT_MAX_N) return (int64_t)B * H * (32 * ((N + 31) / 32)) * 4;
-  if (!long_keep_path(B, H, N)) return 0;  // (320, 384) with few heads: v1 forward, masks re-hashed
-  return (int64_t)B * H * N * ((N + 63) / 64) * 2;
+// one integer per kernel of the list (every field within its radix)
+constexpr int kernel_key(AttnKernel k, int hd, int np, bool drop, bool keep) {
+  return ((((int)k * 4 + hd / 32) * 8 + np / 32) * 2 + (int)drop) * 2 + (int)keep;
 }
 
-void attn_fwd_launch(const void* qkv, void* o, float* lse, int B, int H, int N, int hd, float scale,
-                     const int64_t* rng, int site, double p, hipStream_t stream, uint32_t* keep_bits) {
-  const dim3 grid((N + 63) / 64, B * H);
-  const uint32_t thr = drop_threshold_host(p);
-  const float dsc = p > 0 ? 1.f / (1.f - (float)p) : 1.f;
-  const bf16* q = reinterpret_cast<const bf16*>(qkv);
-  bf16* out = reinterpret_cast<bf16*>(o);
-  if (hd != 32 && hd != 64) throw std::runtime_error("attention: head dim must be 32 or 64");
-  if (N <= SHORT_MAX_N) {
-    if (hd == 32)
-      dispatch_short<32>(false, nullptr, q, nullptr, lse, nullptr, out, B, H, N, scale, rng, site, thr, dsc, stream,
-                         keep_bits);
-    else
-      dispatch_short<64>(false, nullptr, q, nullptr, lse, nullptr, out, B, H, N, scale, rng, site, thr, dsc, stream,
-                         keep_bits);
-    return;
-  }
-  uint32_t* kb = thr ? keep_bits : nullptr;
-  // one workgroup per head: needs ~a workgroup per CU to pay off.  Measured N=257
-  // hd=64: B*H=256 20.1 vs 31.9 us (one 64-query workgroup per tile); B*H=128 equal
-  // without dropout, 27 vs 22 with
-  if (N <= 320 && B * H >= 192) {
-    if (hd == 32) launch_resident<32>(q, out, lse, B, H, N, scale, rng, site, thr, dsc, stream, kb);
-    else launch_resident<64>(q, out, lse, B, H, N, scale, rng, site, thr, dsc, stream, kb);
-    return;
-  }
-  // v2 (128 queries per workgroup) has half the workgroups of v1: measured better from
-  // ~600 tokens (N=626: 63 vs 71 us without dropout), worse at N=257 with dropout (25 vs 22 us)
-  if (N >= 384) {
-    const dim3 grid2((N + 127) / 128, B * H);
-    if (hd == 32) {
-      if (thr) hipLaunchKernelGGL((attn_fwd_flash2_kernel<32, true>), grid2, dim3(256), 0, stream, q, out, lse, B, H, N, scale, rng, site, thr, dsc, kb);
-      else hipLaunchKernelGGL((attn_fwd_flash2_kernel<32, false>), grid2, dim3(256), 0, stream, q, out, lse, B, H, N, scale, rng, site, thr, dsc, kb);
-    } else {
-      if (thr) hipLaunchKernelGGL((attn_fwd_flash2_kernel<64, true>), grid2, dim3(256), 0, stream, q, out, lse, B, H, N, scale, rng, site, thr, dsc, kb);
-      else hipLaunchKernelGGL((attn_fwd_flash2_kernel<64, false>), grid2, dim3(256), 0, stream, q, out, lse, B, H, N, scale, rng, site, thr, dsc, kb);
-    }
-    return;
-  }
-  if (keep_bits != nullptr && thr)
-    throw std::runtime_error("attention: no stored keep masks on this path (attn_keep_words returned 0)");
-  if (hd == 32)
-    hipLaunchKernelGGL(attn_fwd_kernel<32>, grid, dim3(256), 0, stream, q, out, lse, B, H, N, scale, rng, site, thr, dsc);
-  else
-    hipLaunchKernelGGL(attn_fwd_kernel<64>, grid, dim3(256), 0, stream, q, out, lse, B, H, N, scale, rng, site, thr, dsc);
+// Raise a kernel's dynamic-LDS limit to `bytes` where that is above the default: once per
+// kernel, not per call.
+template <auto Kernel>
+static void allow_lds(int bytes) {
+  static const bool once = [bytes] {
+    if (bytes > ATTN_LDS_DEFAULT)
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    return true;
+  }();
+  (void)once;
 }
 
-void attn_bwd_launch(const void* dout, const void* qkv, const void* o, const float* lse, void* dqkv,
-                        float* delta, int B, int H, int N, int hd, float scale, const int64_t* rng, int site,
-                        double p, hipStream_t stream, const uint32_t* keep_bits) {
-  uint32_t* kb = const_cast<uint32_t*>(keep_bits);  // read-only in the backward kernels
-  const dim3 grid((N + 63) / 64, B * H);
-  const uint32_t thr = drop_threshold_host(p);
-  const float dsc = p > 0 ? 1.f / (1.f - (float)p) : 1.f;
-  const bf16* d = reinterpret_cast<const bf16*>(dout);
-  const bf16* q = reinterpret_cast<const bf16*>(qkv);
-  const bf16* oo = reinterpret_cast<const bf16*>(o);
-  bf16* dq = reinterpret_cast<bf16*>(dqkv);
-  if (N <= SHORT_MAX_N && (hd == 32 || hd == 64)) {
-    if (hd == 32) dispatch_short<32>(true, d, q, oo, nullptr, lse, dq, B, H, N, scale, rng, site, thr, dsc, stream, kb);
-    else dispatch_short<64>(true, d, q, oo, nullptr, lse, dq, B, H, N, scale, rng, site, thr, dsc, stream, kb);
-    return;
+// Launch what the plan names: the instantiation whose template arguments equal it.
+static void attn_launch(bool bwd, const AttnArgs& a, hipStream_t stream) {
+  const uint32_t thr = drop_threshold_host(a.p);
+  const float dsc = a.p > 0 ? 1.f / (1.f - (float)a.p) : 1.f;
+  const AttnPlan pl = attn_plan(bwd, a.B, a.H, a.N, a.hd, thr != 0, a.keep != nullptr);
+  const dim3 grid(pl.grid_x, pl.grid_y), block(pl.block);
+  const bf16* q = reinterpret_cast<const bf16*>(a.qkv);
+  const bf16* d = reinterpret_cast<const bf16*>(a.dout);
+  bf16* o = reinterpret_cast<bf16*>(a.o);
+  bf16* dq = reinterpret_cast<bf16*>(a.dqkv);
+  // the keep buffer goes to the long forwards only with dropout on; to the short forward and
+  // the backwards as given (their no-dropout / re-hash instantiations do not touch it)
+  uint32_t* kb_long = thr ? a.keep : nullptr;
+  const AttnKernelArgs t = attn_kernel_args(pl.kernel, pl);
+#define DC_TAIL a.B, a.H, a.N, a.scale, a.rng, a.site, thr, dsc
+#define DC_CASE(K, HD, NP, DR, KB) case kernel_key(AttnKernel::K, HD, NP, DR, KB):
+#define DC_RUN_V1(HD)                                                                                      \
+  DC_CASE(FWD_V1, HD, 0, false, false)                                                                      \
+  hipLaunchKernelGGL(attn_fwd_kernel<HD>, grid, block, 0, stream, q, o, a.lse, DC_TAIL);                    \
+  return;
+#define DC_RUN_FLASH2(HD, DR)                                                                              \
+  DC_CASE(FWD_FLASH2, HD, 0, DR, false)                                                                     \
+  hipLaunchKernelGGL((attn_fwd_flash2_kernel<HD, DR>), grid, block, 0, stream, q, o, a.lse, DC_TAIL, kb_long); \
+  return;
+#define DC_RUN_RESIDENT(HD, DR)                                                                            \
+  DC_CASE(FWD_RESIDENT, HD, 0, DR, false)                                                                   \
+  allow_lds<&attn_fwd_resident_kernel<HD, DR>>(ATTN_LDS_BUDGET);                                            \
+  hipLaunchKernelGGL((attn_fwd_resident_kernel<HD, DR>), grid, block, pl.lds, stream, q, o, a.lse, DC_TAIL, kb_long); \
+  return;
+#define DC_RUN_LONG_BWD(HD, KB)                                                                            \
+  DC_CASE(BWD_DQ, HD, 0, false, KB)                                                                         \
+  hipLaunchKernelGGL((attn_bwd_dq_kernel<HD, 1, KB>), grid, block, 0, stream, d, q, o, a.lse, a.delta, dq, DC_TAIL, a.keep); \
+  hipLaunchKernelGGL((attn_bwd_dkv_kernel<HD, 1, KB>), grid, block, 0, stream, d, q, a.lse, a.delta, dq, DC_TAIL, a.keep); \
+  return;
+#define DC_RUN_SHORT_FWD(HD, NP, DR)                                                                       \
+  DC_CASE(FWD_SHORT, HD, NP, DR, false)                                                                     \
+  allow_lds<&attn_fwd_short_kernel<HD, NP, DR>>(pl.lds);                                                    \
+  hipLaunchKernelGGL((attn_fwd_short_kernel<HD, NP, DR>), grid, block, pl.lds, stream, q, o, a.lse, DC_TAIL, a.keep); \
+  return;
+#define DC_RUN_SHORT_BWD(HD, NP, DR, KB)                                                                   \
+  DC_CASE(BWD_SHORT, HD, NP, DR, KB)                                                                        \
+  allow_lds<&attn_bwd_short_kernel<HD, NP, DR, KB>>(pl.lds);                                                \
+  hipLaunchKernelGGL((attn_bwd_short_kernel<HD, NP, DR, KB>), grid, block, pl.lds, stream, d, q, o, a.lse, dq, DC_TAIL, a.keep); \
+  return;
+  switch (kernel_key(pl.kernel, t.hd, t.np, t.drop, t.keep)) {
+    DC_ATTN_KERNELS(DC_RUN_V1, DC_RUN_FLASH2, DC_RUN_RESIDENT, DC_RUN_LONG_BWD, DC_RUN_SHORT_FWD, DC_RUN_SHORT_BWD)
   }
-  if (hd != 32 && hd != 64) throw std::runtime_error("attention: head dim must be 32 or 64");
-  // one 16-row group per wave (U = 1).  Measured slower and not built: U = 2 (every
-  // LDS fragment feeding two MFMAs; N=626 p=0.1 stored masks 154.1 vs 146.1 us, N=2,501
-  // 448 vs 337: 174 / 236 VGPRs put dQ / dK-dV at 2 waves per SIMD against 4 / 3), and
-  // a dK/dV prefetch two query tiles ahead in two register sets (178 VGPRs, 2 waves per
-  // SIMD: 180 vs 146 us) -- the kernels need the latency hiding of occupancy more
-  const dim3 gridu((N + 63) / 64, B * H);
-#define DC_LAUNCH_BWD(HDV, UV)                                                                                        \
-  if (thr && keep_bits) {                                                                                             \
-    hipLaunchKernelGGL((attn_bwd_dq_kernel<HDV, UV, true>), gridu, dim3(256), 0, stream, d, q, oo, lse, delta, dq, B,  \
-                       H, N, scale, rng, site, thr, dsc, keep_bits);                                                 \
-    hipLaunchKernelGGL((attn_bwd_dkv_kernel<HDV, UV, true>), gridu, dim3(256), 0, stream, d, q, lse, delta, dq, B, H, \
-                       N, scale, rng, site, thr, dsc, keep_bits);                                                    \
-  } else {                                                                                                            \
-    hipLaunchKernelGGL((attn_bwd_dq_kernel<HDV, UV, false>), gridu, dim3(256), 0, stream, d, q, oo, lse, delta, dq,  \
-                       B, H, N, scale, rng, site, thr, dsc, keep_bits);                                              \
-    hipLaunchKernelGGL((attn_bwd_dkv_kernel<HDV, UV, false>), gridu, dim3(256), 0, stream, d, q, lse, delta, dq, B,   \
-                       H, N, scale, rng, site, thr, dsc, keep_bits);                                                 \
-  }
-  if (hd == 32) { DC_LAUNCH_BWD(32, 1) }
-  else { DC_LAUNCH_BWD(64, 1) }
-#undef DC_LAUNCH_BWD
+#undef DC_RUN_V1
+#undef DC_RUN_FLASH2
+#undef DC_RUN_RESIDENT
+#undef DC_RUN_LONG_BWD
+#undef DC_RUN_SHORT_FWD
+#undef DC_RUN_SHORT_BWD
+#undef DC_CASE
+#undef DC_TAIL
+  throw std::logic_error("attention: the plan names a kernel that is not instantiated");
 }
+
+void attn_fwd_launch(const AttnArgs& a, hipStream_t stream) { attn_launch(false, a, stream); }
+void attn_bwd_launch(const AttnArgs& a, hipStream_t stream) { attn_launch(true, a, stream); }

@@ -297,34 +297,53 @@ void gemm_stamps_op(c10::optional<Tensor> buf) {
   }
 }
 
-// attention-dropout keep-flag words the short forward stores for the backward
-// (0: this shape takes the long-sequence kernels, which regenerate the masks)
+// int32 words of the attention-dropout keep flags a forward of this shape stores for the
+// backward (attn_plan.h; 0: the v1 forward, whose masks the backward re-hashes)
 int64_t attn_keep_words_op(int64_t B, int64_t H, int64_t N, int64_t hd) {
   return attn_keep_words((int)B, (int)H, (int)N, (int)hd);
 }
+// the plan both launches follow (host only: no launch), as (path, hd, np, drop, keep,
+// grid x, grid y, block, dynamic LDS bytes, keep words); throws where they would
+std::vector<int64_t> attn_plan_op(bool bwd, int64_t B, int64_t H, int64_t N, int64_t hd, bool drop, bool have_keep) {
+  const AttnPlan pl = attn_plan(bwd, (int)B, (int)H, (int)N, (int)hd, drop, have_keep);
+  return {(int64_t)pl.path, pl.hd, pl.np, pl.drop, pl.keep, pl.grid_x, pl.grid_y, pl.block, pl.lds, pl.keep_words};
+}
 
-static uint32_t* keep_ptr(const c10::optional<Tensor>& keep, int B, int H, int N, int hd) {
-  if (!keep.has_value()) return nullptr;
-  CHECK_IN(keep.value(), at::kInt);
-  const int64_t need = attn_keep_words(B, H, N, hd);
-  TORCH_CHECK(need > 0 && keep->numel() >= need, "attention keep-flag buffer: need ", need, " int32 words");
-  return reinterpret_cast<uint32_t*>(keep->data_ptr<int32_t>());
+// What both attention ops check of qkv, p and the optional keep buffer before anything is
+// allocated or launched; the launch arguments they share.
+static AttnArgs check_attn(const Tensor& qkv, double scale, const Tensor& rng, int64_t site, double p,
+                           const c10::optional<Tensor>& keep) {
+  CHECK_IN(qkv, BF16); check_rng(rng);
+  TORCH_CHECK(qkv.dim() == 5 && qkv.size(0) == 3, "qkv must be [3,B,H,N,hd]");
+  AttnArgs a;
+  a.B = qkv.size(1); a.H = qkv.size(2); a.N = qkv.size(3); a.hd = qkv.size(4);
+  TORCH_CHECK(a.hd == 32 || a.hd == 64, "head dim must be 32 or 64");
+  // dropout mask elements are indexed with 32-bit counters (hoisted pair-hash math)
+  TORCH_CHECK(p <= 0 || (int64_t)a.B * a.H * a.N * ((a.N + 3) & ~3) < ((int64_t)1 << 32),
+              "attention dropout: more than 2^32 mask elements");
+  if (keep.has_value()) {
+    CHECK_IN(keep.value(), at::kInt);
+    const int64_t need = attn_keep_words(a.B, a.H, a.N, a.hd);
+    TORCH_CHECK(need > 0 && keep->numel() >= need, "attention keep-flag buffer: need ", need, " int32 words");
+    a.keep = reinterpret_cast<uint32_t*>(keep->data_ptr<int32_t>());
+  }
+  a.qkv = qkv.data_ptr();
+  a.scale = (float)scale;
+  a.rng = rng.data_ptr<int64_t>();
+  a.site = (int)site;
+  a.p = p;
+  return a;
 }
 
 std::tuple<Tensor, Tensor> attn_fwd(Tensor qkv, double scale, Tensor rng, int64_t site, double p,
                                     c10::optional<Tensor> keep_out) {
-  CHECK_IN(qkv, BF16); check_rng(rng);
+  AttnArgs a = check_attn(qkv, scale, rng, site, p, keep_out);
   const c10::DeviceGuard guard(qkv.device());
-  TORCH_CHECK(qkv.dim() == 5 && qkv.size(0) == 3, "qkv must be [3,B,H,N,hd]");
-  const int B = qkv.size(1), H = qkv.size(2), N = qkv.size(3), hd = qkv.size(4);
-  TORCH_CHECK(hd == 32 || hd == 64, "head dim must be 32 or 64");
-  // dropout mask elements are indexed with 32-bit counters (hoisted pair-hash math)
-  TORCH_CHECK(p <= 0 || (int64_t)B * H * N * ((N + 3) & ~3) < ((int64_t)1 << 32),
-              "attention dropout: more than 2^32 mask elements");
-  auto o = at::empty({B, N, H * hd}, qkv.options());
-  auto lse = at::empty({B, H, N}, qkv.options().dtype(F32));
-  attn_fwd_launch(qkv.data_ptr(), o.data_ptr(), lse.data_ptr<float>(), B, H, N, hd, (float)scale,
-                  rng.data_ptr<int64_t>(), site, p, cur_stream(), keep_ptr(keep_out, B, H, N, hd));
+  auto o = at::empty({a.B, a.N, a.H * a.hd}, qkv.options());
+  auto lse = at::empty({a.B, a.H, a.N}, qkv.options().dtype(F32));
+  a.o = o.data_ptr();
+  a.lse = lse.data_ptr<float>();
+  attn_fwd_launch(a, cur_stream());
   return {o, lse};
 }
 
@@ -968,21 +987,20 @@ void replica_reduce_(Tensor ws, Tensor dst_ptrs, int64_t C, int64_t R) {
 
 Tensor attn_bwd(Tensor dout, Tensor qkv, Tensor o, Tensor lse, double scale, Tensor rng, int64_t site, double p,
                 c10::optional<Tensor> keep) {
-  CHECK_IN(dout, BF16); CHECK_IN(qkv, BF16); CHECK_IN(o, BF16); CHECK_IN(lse, F32); check_rng(rng);
+  CHECK_IN(dout, BF16); CHECK_IN(o, BF16); CHECK_IN(lse, F32);
+  AttnArgs a = check_attn(qkv, scale, rng, site, p, keep);
   const c10::DeviceGuard guard(qkv.device());
-  TORCH_CHECK(qkv.dim() == 5 && qkv.size(0) == 3, "qkv must be [3,B,H,N,hd]");
-  const int B = qkv.size(1), H = qkv.size(2), N = qkv.size(3), hd = qkv.size(4);
-  TORCH_CHECK(hd == 32 || hd == 64, "head dim must be 32 or 64");
-  TORCH_CHECK(dout.numel() == (int64_t)B * N * H * hd && o.numel() == dout.numel() &&
-                  lse.numel() == (int64_t)B * H * N,
+  TORCH_CHECK(dout.numel() == (int64_t)a.B * a.N * a.H * a.hd && o.numel() == dout.numel() &&
+                  lse.numel() == (int64_t)a.B * a.H * a.N,
               "attn_bwd shapes");
-  TORCH_CHECK(p <= 0 || (int64_t)B * H * N * ((N + 3) & ~3) < ((int64_t)1 << 32),
-              "attention dropout: more than 2^32 mask elements");
-  auto dqkv = at::empty({(int64_t)B * N, 3 * H * hd}, qkv.options());
-  auto delta = at::empty({(int64_t)B * H * N}, lse.options());
-  attn_bwd_launch(dout.data_ptr(), qkv.data_ptr(), o.data_ptr(), lse.data_ptr<float>(), dqkv.data_ptr(),
-                  delta.data_ptr<float>(), B, H, N, hd, (float)scale, rng.data_ptr<int64_t>(), site, p,
-                  cur_stream(), keep_ptr(keep, B, H, N, hd));
+  auto dqkv = at::empty({(int64_t)a.B * a.N, 3 * a.H * a.hd}, qkv.options());
+  auto delta = at::empty({(int64_t)a.B * a.H * a.N}, lse.options());
+  a.dout = dout.data_ptr();
+  a.o = o.data_ptr();
+  a.lse = lse.data_ptr<float>();
+  a.dqkv = dqkv.data_ptr();
+  a.delta = delta.data_ptr<float>();
+  attn_bwd_launch(a, cur_stream());
   return dqkv;
 }
 
@@ -1277,6 +1295,7 @@ TORCH_LIBRARY(ddim_cold, m) {
         "float ln_eps=1e-5, Tensor(a!)? ln_mean=None, Tensor(b!)? ln_rstd=None) -> Tensor");
   m.def("attn_fwd(Tensor qkv, float scale, Tensor rng, int site, float p, Tensor? keep_out=None) -> (Tensor, Tensor)");
   m.def("attn_keep_words(int B, int H, int N, int hd) -> int", &attn_keep_words_op);
+  m.def("attn_plan(bool bwd, int B, int H, int N, int hd, bool drop, bool have_keep) -> int[]", &attn_plan_op);
   m.def("gemm_tile_override(int cfg) -> int", &gemm_tile_override_op);
   m.def("gemm_plan(int epi, bool at, bool bt, int M, int N, int K, int splits=1) -> int[]", &gemm_plan_op);
   m.def("gemm_stamps(Tensor? buf) -> ()", &gemm_stamps_op);

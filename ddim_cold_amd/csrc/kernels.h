@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdexcept>
+#include "attn_plan.h"
 #include "gemm_plan.h"
 #include "wgrad_plan.h"
 
@@ -160,16 +161,27 @@ void ln_fold_launch(const FoldTable& tb, hipStream_t stream);
 // ws [G][rows][C]: sums rows 0..R-1 of each workspace
 void replica_reduce_launch(const float* ws, float* const* dsts_dev, int G, int C, int R, int rows, hipStream_t stream);
 
-// Attention (attention.hip)
-// keep_bits: optional [attn_keep_words] attention-dropout keep flags, written by
-// the short-sequence forward and read by its backward instead of re-hashing
-// (ignored by the long-sequence kernels, which always regenerate)
-int64_t attn_keep_words(int B, int H, int N, int hd);
-void attn_fwd_launch(const void* qkv, void* o, float* lse, int B, int H, int N, int hd, float scale,
-                     const int64_t* rng, int site, double p, hipStream_t stream, uint32_t* keep_bits = nullptr);
-void attn_bwd_launch(const void* dout, const void* qkv, const void* o, const float* lse, void* dqkv,
-                     float* delta, int B, int H, int N, int hd, float scale, const int64_t* rng, int site,
-                     double p, hipStream_t stream, const uint32_t* keep_bits = nullptr);
+// Attention (attention.hip).  Both launches follow attn_plan (attn_plan.h) and throw where
+// it does.
+struct AttnArgs {
+  const void* qkv = nullptr;  // [3,B,H,N,hd] bf16, head-major
+  void* o = nullptr;          // [B,N,H*hd] bf16: written by the forward, read by the backward
+  float* lse = nullptr;       // [B,H,N]: likewise
+  const void* dout = nullptr;  // backward only: [B,N,H*hd] bf16
+  void* dqkv = nullptr;        //   [B*N, 3*H*hd] bf16 out
+  float* delta = nullptr;      //   [B,H,N] workspace (long sequences)
+  int B = 0, H = 0, N = 0, hd = 0;
+  float scale = 1.f;
+  const int64_t* rng = nullptr;
+  int site = 0;
+  double p = 0.0;
+  // optional [attn_keep_words] attention-dropout keep flags: with dropout on, the forward
+  // (short, resident, flash v2) writes them and the backward reads them instead of
+  // re-hashing the masks.  The v1 forward stores none (attn_keep_words is 0 there).
+  uint32_t* keep = nullptr;
+};
+void attn_fwd_launch(const AttnArgs& a, hipStream_t stream);
+void attn_bwd_launch(const AttnArgs& a, hipStream_t stream);
 
 // Embedding / head / loss (embed.hip)
 // Optional cold-diffusion batch source fused into patchify (pool != nullptr): the

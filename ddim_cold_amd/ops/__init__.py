@@ -18,7 +18,7 @@ from . import reference as ref
 from ._ext import force_reference
 
 __all__ = [
-    "native_available", "patch_embed_fwd", "layernorm_fwd", "qkv_fwd", "attn_fwd", "attn_keep_buffer",
+    "native_available", "patch_embed_fwd", "layernorm_fwd", "qkv_fwd", "attn_fwd", "attn_keep_buffer", "attn_plan",
     "linear_residual_fwd", "linear_gelu_fwd", "head_fwd", "smooth_l1_fwd_bwd", "img_to_tokgrad",
     "linear_dgrad", "linear_dgrad_gelu", "linear_wgrad", "layernorm_bwd", "attn_bwd", "embed_bwd",
     "sqnorm", "adamw_step", "weight_ema_decay", "advance_counters", "ddim_step", "ddim_step_", "randn_", "q_sample",
@@ -147,12 +147,44 @@ class gemm_tile:
         return False
 
 
+ATTN_PATHS = ("short", "v1", "resident", "flash2")
+
+
+class AttnPlan(NamedTuple):
+    """What an attention launch gets (csrc/attn_plan.h): the forward ``path`` of the shape
+    (one of :data:`ATTN_PATHS`; the backward of every path but ``short`` is the dQ and dK/dV
+    kernel pair), the short path's padded rows ``np`` (else 0), whether the dropout kernels
+    run (``drop``) and whether they store / read keep flags (``keep``), the launch geometry,
+    and the int32 ``keep_words`` a keep buffer of the shape holds."""
+    path: str
+    hd: int
+    np: int
+    drop: bool
+    keep: bool
+    grid_x: int
+    grid_y: int
+    block: int
+    lds: int
+    keep_words: int
+
+
+def attn_plan(bwd: bool, B: int, H: int, N: int, hd: int, drop: bool, have_keep: bool) -> AttnPlan:
+    """The plan ``attn_fwd`` (``bwd`` false) / ``attn_bwd`` follow: the same function as the
+    launches call, so it raises where they would (a head dim other than 32 or 64, a keep
+    buffer with dropout on where the v1 forward runs).  ``drop``: the dropout threshold of
+    ``p`` is not 0.  Host only: launches nothing."""
+    _ext.load(raise_on_error=True)
+    v = [int(x) for x in _ops().attn_plan(bool(bwd), B, H, N, hd, bool(drop), bool(have_keep))]
+    return AttnPlan(ATTN_PATHS[v[0]], v[1], v[2], bool(v[3]), bool(v[4]), *v[5:])
+
+
 def attn_keep_buffer(qkv, p: float):
     """int32 buffer for the attention-dropout keep flags the forward stores for its
     backward (short sequences: one word per lane; long ones: one 64-bit word per
     query and 64-key tile), so the backward reads masks instead of re-hashing them;
     None when there is nothing to store (p = 0, CPU, or the one long-sequence
-    forward that keeps no words: 320 < N < 384 with fewer than 192 heads)."""
+    forward that keeps no words, v1: 128 < N < 384 with fewer than 192 heads, and
+    320 < N < 384 with any number)."""
     if p <= 0 or not _hip(qkv):
         return None
     _, B, H, N, hd = qkv.shape

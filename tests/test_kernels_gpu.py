@@ -627,6 +627,8 @@ def test_attention_tile_edges(path, B, H, N, hd, p):
     and backward against the fp64 truth, with re-hashed and with stored dropout masks."""
     assert {"short": N <= 128, "v1": 128 < N < 384 and B * H < 192, "resident": 128 < N <= 320 and B * H >= 192,
             "flash2": N >= 384}[path]
+    plans = [ops.attn_plan(bwd, B, H, N, hd, p > 0, False) for bwd in (False, True)]
+    assert [pl.path for pl in plans] == [path, path]
     qkv = bf(3, B, H, N, hd)
     do = bf(B, N, H * hd)
     r = rng()
@@ -640,9 +642,25 @@ def test_attention_tile_edges(path, B, H, N, hd, p):
     keep = ops.attn_keep_buffer(qkv, p)
     assert (keep is not None) == (p > 0 and path != "v1")
     if keep is not None:  # stored keep words: the same bits, so the same outputs
+        assert keep.numel() == plans[0].keep_words == plans[1].keep_words
         o2, lse2 = ops.attn_fwd(qkv, scale, r, 5, p, keep_out=keep)
         assert torch.equal(o2, o) and torch.equal(lse2, lse), "forward storing keep words"
         assert torch.equal(ops.attn_bwd(do, qkv, o, lse, scale, r, 5, p, keep=keep), dq), "backward from keep words"
+
+
+def test_attention_keep_buffer_refused_on_v1():
+    """The v1 forward's shapes (here 2 heads of 129 tokens) store no dropout masks: a keep
+    buffer handed to either op with dropout on is refused before anything launches."""
+    B, H, N, hd, p = 1, 2, 129, 32, 0.1
+    assert ops.attn_plan(False, B, H, N, hd, True, False).path == "v1"
+    qkv = torch.zeros(3, B, H, N, hd, dtype=torch.bfloat16, device=DEV)
+    o = torch.zeros(B, N, H * hd, dtype=torch.bfloat16, device=DEV)
+    lse = torch.zeros(B, H, N, device=DEV)
+    word = torch.zeros(1, dtype=torch.int32, device=DEV)
+    with pytest.raises(RuntimeError):
+        ops.attn_fwd(qkv, hd ** -0.5, rng(), 5, p, keep_out=word)
+    with pytest.raises(RuntimeError):
+        ops.attn_bwd(o, qkv, o, lse, hd ** -0.5, rng(), 5, p, keep=word)
 
 
 # one N per kernel path: short, v1, resident, flash v2, flash v2 at the benchmark length
