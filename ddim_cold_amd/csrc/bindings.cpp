@@ -162,35 +162,54 @@ std::tuple<Tensor, Tensor> patch_embed_fwd(Tensor img, Tensor t, Tensor w_pe, Te
                           patches_in);
 }
 
-// Pool indices of a batch source that reads them (!draw_idx): a [B] vector, or with
-// `ctr` a stepped table [rows][...] read at row ctr[0] % rows, elements off..off+B
-// (the trainer's epoch DistributedSampler table indexed by the device step counter).
-struct IdxSel {
-  int64_t* p;
-  const int64_t* ctr;
-  int rows, stride;
-};
-static IdxSel idx_select(const Tensor& idx, const c10::optional<Tensor>& ctr, int64_t off, int B, bool draw_idx,
-                         const char* what) {
+// The batch source (ColdSrc, kernels.h) of patch_embed_cold_fwd, cold_batch and gauss_batch:
+// what the three share, checked once.  `img` is the [B,C,H,W] x_t buffer whose shape drives
+// the launch; pool [*,C,H,W], target like img, t [B], all on img's device.  Pool indices that
+// are read (!draw_idx): a [B] vector, or with `ctr` a stepped table [rows][...] read at row
+// ctr[0] % rows, elements off..off+B (the trainer's epoch DistributedSampler table indexed by
+// the device step counter).  Each op adds its own fields (site, max_t / gauss_T, x_t, ...).
+ColdSrc batch_source(const Tensor& pool, const Tensor& img, const Tensor& target, const Tensor& t, const Tensor& idx,
+                     const c10::optional<Tensor>& ctr, int64_t off, bool draw_idx, const char* what) {
+  CHECK_IN(pool, F32); CHECK_IN(img, F32); CHECK_IN(target, F32); CHECK_IN(t, I64); CHECK_IN(idx, I64);
+  const auto dev = img.device();
+  TORCH_CHECK(pool.device() == dev && target.device() == dev && t.device() == dev && idx.device() == dev, what,
+              ": pool, target, t and idx must be on the image's device");
+  TORCH_CHECK(img.dim() == 4, what, ": the image buffer must be [B,C,H,W]");
+  const int B = img.size(0);
+  TORCH_CHECK(pool.dim() == 4 && pool.sizes().slice(1) == img.sizes().slice(1), what, ": pool must be [*,C,H,W]");
+  TORCH_CHECK(target.sizes() == img.sizes() && t.numel() == B, what, ": target / t shapes");
+  ColdSrc cs;
+  cs.pool = pool.data_ptr<float>(); cs.pool_n = pool.size(0);
+  cs.idx = idx.data_ptr<int64_t>(); cs.draw_idx = draw_idx;
+  cs.t_out = t.data_ptr<int64_t>(); cs.target = target.data_ptr<float>();
   if (ctr.has_value() && ctr->defined()) {
     CHECK_IN((*ctr), I64);
-    TORCH_CHECK(ctr->device() == idx.device() && ctr->numel() >= 1, what, ": step counter");
+    TORCH_CHECK(ctr->device() == dev && ctr->numel() >= 1, what, ": step counter");
     TORCH_CHECK(!draw_idx, what, ": a stepped index table is read, not drawn");
     TORCH_CHECK(idx.dim() >= 2 && idx.size(0) >= 1, what, ": a stepped index table is [rows, ...]");
     const int64_t rows = idx.size(0), stride = idx.numel() / rows;
     TORCH_CHECK(off >= 0 && off + B <= stride && idx.numel() < ((int64_t)1 << 31), what,
                 ": batch offset outside the table row");
-    return {idx.data_ptr<int64_t>() + off, ctr->data_ptr<int64_t>(), (int)rows, (int)stride};
+    cs.idx += off;
+    cs.idx_ctr = ctr->data_ptr<int64_t>(); cs.idx_rows = (int)rows; cs.idx_stride = (int)stride;
+  } else {
+    TORCH_CHECK(idx.numel() == B && off == 0, what, ": idx shape");
   }
-  TORCH_CHECK(idx.numel() == B && off == 0, what, ": idx shape");
-  return {idx.data_ptr<int64_t>(), nullptr, 1, 0};
+  return cs;
+}
+
+// The coarsest cold level is one 2^max_t block: it has to fit the width, and with `and_h`
+// the height (the fused patchify asks for both, cold_batch has only ever asked for W).
+void check_max_t(int64_t max_t, int H, int W, bool and_h) {
+  TORCH_CHECK(max_t >= 1 && max_t <= 30, "max_t must be in 1..30");
+  const int64_t f = (int64_t)1 << max_t;
+  TORCH_CHECK(f <= W && (!and_h || f <= H), "max_t");
 }
 
 // patch_embed_fwd with the cold-diffusion batch draw fused into the patchify launch
-// (cold_batch + patch_embed_fwd in one launch fewer): `img` is the x_t buffer (its
-// shape drives the launch; written only if write_xt), `target`, `t` and `idx` are outputs
-// (idx is an input when !draw_idx).  Same values as ops.cold_batch followed by
-// patch_embed_fwd on its x_t.
+// (cold_batch + patch_embed_fwd in one launch fewer): `img` is the x_t buffer (written
+// only if write_xt), `target`, `t` and `idx` are outputs (idx is an input when
+// !draw_idx).  Same values as ops.cold_batch followed by patch_embed_fwd on its x_t.
 std::tuple<Tensor, Tensor> patch_embed_cold_fwd(Tensor pool, int64_t data_site, int64_t max_t, bool draw_idx,
                                                 bool target_x0, Tensor img, Tensor target, Tensor t, Tensor idx,
                                                 bool write_xt, Tensor w_pe, Tensor b_pe, Tensor cls, Tensor pos,
@@ -198,34 +217,16 @@ std::tuple<Tensor, Tensor> patch_embed_cold_fwd(Tensor pool, int64_t data_site, 
                                                 c10::optional<Tensor> ln_st, c10::optional<Tensor> xb_out,
                                                 int64_t gauss_T, int64_t noise_site, bool target_rows,
                                                 c10::optional<Tensor> idx_ctr, int64_t idx_off) {
-  CHECK_IN(pool, F32); CHECK_IN(img, F32); CHECK_IN(target, F32); CHECK_IN(t, I64); CHECK_IN(idx, I64);
-  const int B = img.size(0), C = img.size(1), H = img.size(2), W = img.size(3);
-  TORCH_CHECK(pool.dim() == 4 && pool.size(1) == C && pool.size(2) == H && pool.size(3) == W, "pool shape");
-  TORCH_CHECK(target.sizes() == img.sizes() && t.numel() == B, "cold patch-embed shapes");
-  const IdxSel is = idx_select(idx, idx_ctr, idx_off, B, draw_idx, "cold patch-embed");
+  ColdSrc cs = batch_source(pool, img, target, t, idx, idx_ctr, idx_off, draw_idx, "cold patch-embed");
   if (gauss_T > 0) {
     TORCH_CHECK(target_x0, "Gaussian batch: the target is x0");
     TORCH_CHECK(gauss_T <= temb.size(0), "Gaussian batch: T exceeds the time-embedding rows");
-    TORCH_CHECK((int64_t)B * C * H * W < ((int64_t)1 << 31), "Gaussian batch: 32-bit noise index");
+    TORCH_CHECK(img.numel() < ((int64_t)1 << 31), "Gaussian batch: 32-bit noise index");
   } else {
-    TORCH_CHECK(max_t >= 1 && (1 << max_t) <= W && (1 << max_t) <= H, "max_t");
+    check_max_t(max_t, img.size(2), img.size(3), true);
   }
-  ColdSrc cs;
-  cs.gauss_T = gauss_T;
-  cs.noise_site = noise_site;
-  cs.target_rows = target_rows;
-  cs.pool = pool.data_ptr<float>();
-  cs.pool_n = pool.size(0);
-  cs.site = data_site;
-  cs.max_t = max_t;
-  cs.draw_idx = draw_idx;
-  cs.target_x0 = target_x0;
-  cs.idx = is.p;
-  cs.idx_ctr = is.ctr;
-  cs.idx_rows = is.rows;
-  cs.idx_stride = is.stride;
-  cs.t_out = t.data_ptr<int64_t>();
-  cs.target = target.data_ptr<float>();
+  cs.site = data_site; cs.max_t = max_t; cs.gauss_T = gauss_T; cs.noise_site = noise_site;
+  cs.target_x0 = target_x0; cs.target_rows = target_rows;
   cs.x_t = write_xt ? img.data_ptr<float>() : nullptr;
   return patch_embed_impl(img, t, w_pe, b_pe, cls, pos, temb, rng, site, p, patch, ln_st, xb_out, cs);
 }
@@ -1196,32 +1197,24 @@ std::tuple<Tensor, Tensor> pixelate_pair(Tensor img, c10::optional<Tensor> idx, 
 // Gaussian DDIM batch (GaussianBatcher): x_t = q_sample(pool[idx], t, eps), x0 = pool[idx]
 void gauss_batch(Tensor pool, Tensor rng, int64_t site, int64_t noise_site, int64_t T, Tensor x_t, Tensor x0,
                  Tensor t, Tensor idx, bool draw_idx, c10::optional<Tensor> idx_ctr, int64_t idx_off) {
-  CHECK_IN(pool, F32); check_rng(rng); CHECK_IN(x_t, F32); CHECK_IN(x0, F32); CHECK_IN(t, I64); CHECK_IN(idx, I64);
-  const c10::DeviceGuard guard(pool.device());
-  TORCH_CHECK(x_t.dim() == 4, "gauss_batch: x_t must be [B,C,H,W]");
-  const int B = x_t.size(0), C = x_t.size(1), H = x_t.size(2), W = x_t.size(3);
-  TORCH_CHECK(pool.dim() == 4 && pool.size(1) == C && pool.size(2) == H && pool.size(3) == W, "pool shape");
-  TORCH_CHECK(x0.sizes() == x_t.sizes() && t.numel() == B, "gauss_batch shapes");
-  TORCH_CHECK(T >= 1 && (int64_t)B * C * H * W < ((int64_t)1 << 31), "gauss_batch: T / size");
-  const IdxSel is = idx_select(idx, idx_ctr, idx_off, B, draw_idx, "gauss_batch");
-  gauss_batch_launch(pool.data_ptr<float>(), pool.size(0), rng.data_ptr<int64_t>(), site, noise_site, T,
-                     x_t.data_ptr<float>(), x0.data_ptr<float>(), t.data_ptr<int64_t>(), is.p,
-                     draw_idx, B, C, H, W, cur_stream(), is.ctr, is.rows, is.stride);
+  check_rng(rng);
+  ColdSrc cs = batch_source(pool, x_t, x0, t, idx, idx_ctr, idx_off, draw_idx, "gauss_batch");
+  const c10::DeviceGuard guard(x_t.device());
+  TORCH_CHECK(T >= 1 && x_t.numel() < ((int64_t)1 << 31), "gauss_batch: T / size");
+  cs.site = site; cs.gauss_T = T; cs.noise_site = noise_site; cs.target_x0 = true;
+  cs.x_t = x_t.data_ptr<float>();
+  gauss_batch_launch(cs, rng.data_ptr<int64_t>(), x_t.size(0), x_t.size(1), x_t.size(2), x_t.size(3), cur_stream());
 }
 
 void cold_batch(Tensor pool, Tensor rng, int64_t site, Tensor x_t, Tensor x_tm1, Tensor t, Tensor idx_ws,
                 int64_t max_t, bool draw_idx, c10::optional<Tensor> idx_ctr, int64_t idx_off) {
-  CHECK_IN(pool, F32); check_rng(rng); CHECK_IN(x_t, F32); CHECK_IN(x_tm1, F32); CHECK_IN(t, I64);
-  CHECK_IN(idx_ws, I64);
-  const c10::DeviceGuard guard(pool.device());
-  const int B = x_t.size(0), C = x_t.size(1), H = x_t.size(2), W = x_t.size(3);
-  TORCH_CHECK(pool.dim() == 4 && pool.size(1) == C && pool.size(2) == H && pool.size(3) == W, "pool shape");
-  TORCH_CHECK(x_tm1.sizes() == x_t.sizes() && t.numel() == B, "cold_batch shapes");
-  TORCH_CHECK(max_t >= 1 && (1 << max_t) <= W, "max_t");
-  const IdxSel is = idx_select(idx_ws, idx_ctr, idx_off, B, draw_idx, "cold_batch");
-  cold_batch_launch(pool.data_ptr<float>(), pool.size(0), rng.data_ptr<int64_t>(), site, x_t.data_ptr<float>(),
-                    x_tm1.data_ptr<float>(), t.data_ptr<int64_t>(), is.p, B, C, H, W, max_t,
-                    draw_idx, cur_stream(), is.ctr, is.rows, is.stride);
+  check_rng(rng);
+  ColdSrc cs = batch_source(pool, x_t, x_tm1, t, idx_ws, idx_ctr, idx_off, draw_idx, "cold_batch");
+  const c10::DeviceGuard guard(x_t.device());
+  check_max_t(max_t, x_t.size(2), x_t.size(3), false);
+  cs.site = site; cs.max_t = max_t;
+  cs.x_t = x_t.data_ptr<float>();
+  cold_batch_launch(cs, rng.data_ptr<int64_t>(), x_t.size(0), x_t.size(1), x_t.size(2), x_t.size(3), cur_stream());
 }
 
 

@@ -78,18 +78,9 @@ __global__ __launch_bounds__(256) void pixelate_pair_kernel(const float* __restr
   }
 }
 
-__global__ void cold_draw_kernel(const int64_t* __restrict__ rng, int site, int pool_n, int max_t, int B,
-                                 int64_t* __restrict__ idx, int64_t* __restrict__ t, int draw_idx) {
-  const uint32_t salt = site_salt(rng, site);
-  for (int b = threadIdx.x; b < B; b += blockDim.x) {
-    if (draw_idx) idx[b] = mix32(((uint32_t)(2 * b) * 0x9E3779B1u) ^ salt) % (uint32_t)pool_n;
-    t[b] = 1 + mix32(((uint32_t)(2 * b + 1) * 0x9E3779B1u) ^ salt) % (uint32_t)max_t;
-  }
-}
-
-// cold_draw + pixelate_pair in ONE launch: every element recomputes its sample's
-// (pool index, t) from the counter hash (two mix32, cheaper than a dependent
-// launch); the first element of each sample also stores them for the model.
+// The batch draw + pixelate_pair in ONE launch: every element recomputes its sample's
+// (pool index, t) from the counter hash (cold_draw_idx / cold_draw_t: two mix32, cheaper
+// than a dependent launch); the first element of each sample also stores them for the model.
 __global__ __launch_bounds__(256) void cold_batch_kernel(const float* __restrict__ pool, int pool_n,
                                                          const int64_t* __restrict__ rng, int site, int max_t,
                                                          int64_t* __restrict__ idx, int64_t* __restrict__ t,
@@ -103,9 +94,8 @@ __global__ __launch_bounds__(256) void cold_batch_kernel(const float* __restrict
   for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) {
     const int b = (int)(e / per);
     const int64_t rem = e - (int64_t)b * per;
-    const int64_t src = draw_idx ? (int64_t)(mix32(((uint32_t)(2 * b) * 0x9E3779B1u) ^ salt) % (uint32_t)pool_n)
-                                 : idx[b];
-    const int tt = 1 + (int)(mix32(((uint32_t)(2 * b + 1) * 0x9E3779B1u) ^ salt) % (uint32_t)max_t);
+    const int64_t src = draw_idx ? (int64_t)(uint32_t)cold_draw_idx(salt, b, pool_n) : idx[b];  // (never negative)
+    const int tt = cold_draw_t(salt, b, max_t);
     if (rem == 0) {
       if (draw_idx) idx[b] = src;
       t[b] = tt;
@@ -265,17 +255,15 @@ void pixelate_pair_launch(const float* img, const int64_t* idx, const int64_t* t
                      x_t, x_tm1, B, C, H, W);
 }
 
-void gauss_batch_launch(const float* pool, int pool_n, const int64_t* rng, int site, int noise_site, int T,
-                        float* x_t, float* x0, int64_t* t, int64_t* idx, bool draw_idx, int B, int C, int H, int W,
-                        hipStream_t stream, const int64_t* idx_ctr, int idx_rows, int idx_stride) {
+void gauss_batch_launch(const ColdSrc& cs, const int64_t* rng, int B, int C, int H, int W, hipStream_t stream) {
   const int per = C * H * W;
-  hipLaunchKernelGGL(gauss_batch_kernel, dim3(g_grid((int64_t)B * per)), dim3(256), 0, stream, pool, pool_n, rng, site,
-                     noise_site, T, idx, t, draw_idx ? 1 : 0, x_t, x0, B, per, idx_ctr, idx_rows, idx_stride);
+  hipLaunchKernelGGL(gauss_batch_kernel, dim3(g_grid((int64_t)B * per)), dim3(256), 0, stream, cs.pool, cs.pool_n, rng,
+                     cs.site, cs.noise_site, cs.gauss_T, cs.idx, cs.t_out, cs.draw_idx ? 1 : 0, cs.x_t, cs.target, B,
+                     per, cs.idx_ctr, cs.idx_rows, cs.idx_stride);
 }
 
-void cold_batch_launch(const float* pool, int pool_n, const int64_t* rng, int site, float* x_t, float* x_tm1,
-                       int64_t* t, int64_t* idx_ws, int B, int C, int H, int W, int max_t, bool draw_idx,
-                       hipStream_t stream, const int64_t* idx_ctr, int idx_rows, int idx_stride) {
-  hipLaunchKernelGGL(cold_batch_kernel, dim3(g_grid((int64_t)B * C * H * W)), dim3(256), 0, stream, pool, pool_n, rng,
-                     site, max_t, idx_ws, t, draw_idx ? 1 : 0, x_t, x_tm1, B, C, H, W, idx_ctr, idx_rows, idx_stride);
+void cold_batch_launch(const ColdSrc& cs, const int64_t* rng, int B, int C, int H, int W, hipStream_t stream) {
+  hipLaunchKernelGGL(cold_batch_kernel, dim3(g_grid((int64_t)B * C * H * W)), dim3(256), 0, stream, cs.pool, cs.pool_n,
+                     rng, cs.site, cs.max_t, cs.idx, cs.t_out, cs.draw_idx ? 1 : 0, cs.x_t, cs.target, B, C, H, W,
+                     cs.idx_ctr, cs.idx_rows, cs.idx_stride);
 }

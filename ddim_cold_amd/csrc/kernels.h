@@ -184,9 +184,12 @@ void attn_fwd_launch(const AttnArgs& a, hipStream_t stream);
 void attn_bwd_launch(const AttnArgs& a, hipStream_t stream);
 
 // Embedding / head / loss (embed.hip)
-// Optional cold-diffusion batch source fused into patchify (pool != nullptr): the
-// patch rows are pixelated straight from the pool (cold_batch_kernel's draw), the
+// A training batch source: what the batch is drawn from and where it goes.  Three
+// consumers read it.  patchify (optional there: pool != nullptr) has the draw fused in:
+// the patch rows are pixelated straight from the pool (cold_batch_kernel's draw), the
 // target image and (t, pool index) are written by the same launch; `img` is unused.
+// cold_batch_launch and gauss_batch_launch are the same draw on its own: they write x_t and
+// target as images and read neither target_x0 (the caller gathers x0) nor target_rows.
 struct ColdSrc {
   const float* pool = nullptr;
   int pool_n = 0, site = 0, max_t = 1;
@@ -207,10 +210,8 @@ struct ColdSrc {
   const int64_t* idx_ctr = nullptr;
   int idx_rows = 1, idx_stride = 0;
 };
-// Gaussian DDIM batch on device in one launch (pool draw, noise, q_sample)
-void gauss_batch_launch(const float* pool, int pool_n, const int64_t* rng, int site, int noise_site, int T,
-                        float* x_t, float* x0, int64_t* t, int64_t* idx, bool draw_idx, int B, int C, int H, int W,
-                        hipStream_t stream, const int64_t* idx_ctr = nullptr, int idx_rows = 1, int idx_stride = 0);
+// Gaussian DDIM batch on device in one launch (pool draw, noise, q_sample; diffusion.hip)
+void gauss_batch_launch(const ColdSrc& cs, const int64_t* rng, int B, int C, int H, int W, hipStream_t stream);
 void patchify_cls_launch(const float* img, const int64_t* t, const float* cls, const float* pos,
                          const float* temb, void* patches, float* x, int B, int C, int H, int W, int patch,
                          int D, const int64_t* rng, int site, double p, float* st, void* xb, hipStream_t stream,
@@ -288,9 +289,7 @@ void cold_step_launch(float* x, const float* x0, const int64_t* t, void* patches
 void randn_launch(float* out, int64_t n, const int64_t* rng, int site, hipStream_t stream);
 void q_sample_launch(const float* x0, const int64_t* t, const float* eps, float* out, int B, int64_t per,
                      int total_steps, hipStream_t stream);
-void cold_batch_launch(const float* pool, int pool_n, const int64_t* rng, int site, float* x_t, float* x_tm1,
-                       int64_t* t, int64_t* idx_ws, int B, int C, int H, int W, int max_t, bool draw_idx,
-                       hipStream_t stream, const int64_t* idx_ctr = nullptr, int idx_rows = 1, int idx_stride = 0);
+void cold_batch_launch(const ColdSrc& cs, const int64_t* rng, int B, int C, int H, int W, hipStream_t stream);
 
 // gradient wire format (comm_wire.hip): fp32 <-> bf16 (RNE), 16-B aligned buffers
 void wire_pack_launch(const float* src, void* dst, int64_t n, hipStream_t stream);

@@ -39,80 +39,77 @@ def synthetic_pool(n: int, size=(64, 64), channels: int = 3, seed: int = 0, devi
     return img.clamp(-1, 1).contiguous().to(device)
 
 
-class ColdBatcher:
-    """Device-side cold-diffusion batch source (graph-capturable).
+class _Batcher:
+    """Device-side batch source (graph-capturable): static buffers (x_t, target, t; a subclass
+    allocates and names the target) and the :class:`ops.BatchSource` (:meth:`source`) that
+    says how a batch is drawn into them.
 
-    Each call draws t ~ U{1..max_t} (and, unless ``idx`` is given, B pool
-    indices) from the engine's RNG state and writes (x_t, target, t) into static
-    buffers.  target = x_{t-1} (``ColdDownSampleDataset``) or x0 (``target='x0'``,
-    ``ColdDownSampleDataset_au``).  With ``idx`` (a static device int64[B] the host
-    fills each step from a shard table) the batch follows DistributedSampler order;
-    with ``idx_step = (ctr, off)`` as well, ``idx`` is the whole epoch table and the
-    batch reads its row ``ctr[0] % rows`` (:func:`ops.stepped_idx`) -- no host copy.
+    Each call draws t (and, unless ``idx`` is given, B pool indices) from the engine's RNG
+    state and writes the buffers.  With ``idx`` (a static device int64[B] the host fills
+    each step from a shard table) the batch follows DistributedSampler order; with
+    ``idx_step = (ctr, off)`` as well, ``idx`` is the whole epoch table and the batch reads
+    its row ``ctr[0] % rows`` (:func:`ops.stepped_idx`) -- no host copy.
     """
 
-    def __init__(self, pool: torch.Tensor, batch: int, rng: torch.Tensor, max_t: int | None = None,
-                 target: str = "prev", idx: torch.Tensor | None = None, idx_step=None):
+    def __init__(self, pool: torch.Tensor, batch: int, rng: torch.Tensor, idx: torch.Tensor | None, idx_step):
         self.pool = pool
         B, (C, H, W) = batch, pool.shape[1:]
-        self.max_t = max_t or int(math.log2(W))
         dev = pool.device
         self.x_t = torch.empty(B, C, H, W, device=dev)
-        self.x_tm1 = torch.empty(B, C, H, W, device=dev)
         self.t = torch.empty(B, dtype=torch.int64, device=dev)
         self.draw = idx is None
         self.idx = torch.empty(B, dtype=torch.int64, device=dev) if idx is None else idx
         self.rng = rng
-        self.target = target
         self.idx_step = idx_step
+
+    def source(self) -> ops.BatchSource:
+        raise NotImplementedError
 
     def fused_spec(self):
         """Deferred form for a consumer that fuses the draw into its patch embedding
-        (:func:`ops.patch_embed_cold_fwd`): ``((x_t, target, t), cold)`` without launching
-        anything; x_t is not materialised (the patch rows are pixelated from the pool)."""
-        cold = (self.pool, SITE_DATA, self.max_t, self.draw, self.target == "x0", self.x_tm1, self.idx, False, 0, 0,
-                self.idx_step)
-        return (self.x_t, self.x_tm1, self.t), cold
+        (:func:`ops.patch_embed_cold_fwd`): ``((x_t, target, t), source())`` without launching
+        anything; x_t is not materialised (the patch rows come straight from the pool)."""
+        src = self.source()
+        return (self.x_t, src.target, self.t), src
 
     def __call__(self):
-        ops.cold_batch(self.pool, self.rng, SITE_DATA, self.x_t, self.x_tm1, self.t, self.idx, self.max_t,
-                       self.draw, idx_step=self.idx_step)
-        if self.target == "x0":
-            torch.index_select(self.pool, 0, ops.stepped_idx(self.idx, self.idx_step, self.t.shape[0]),
-                               out=self.x_tm1)
-        return self.x_t, self.x_tm1, self.t
+        src = self.source()
+        ops.batch_draw(src, self.rng, self.x_t, self.t)
+        return self.x_t, src.target, self.t
 
 
-class GaussianBatcher:
-    """Device-side Gaussian DDIM batch source: (q_sample(x0, t, eps), x0, t), t ~ U{0..T-1}
-    (``DiffusionDataset``, diffusion_loader.py:24-58).  One launch (:func:`ops.gauss_batch`:
-    pool draw + noise + q_sample), or none at all when the engine fuses the draw into
-    its patch-embedding launch (:meth:`fused_spec`, same values)."""
+class ColdBatcher(_Batcher):
+    """Cold-diffusion batches: t ~ U{1..max_t}, x_t the pool image pixelated by 2^t, target =
+    x_{t-1} (``ColdDownSampleDataset``) or x0 (``target='x0'``, ``ColdDownSampleDataset_au``)."""
+
+    def __init__(self, pool: torch.Tensor, batch: int, rng: torch.Tensor, max_t: int | None = None,
+                 target: str = "prev", idx: torch.Tensor | None = None, idx_step=None):
+        super().__init__(pool, batch, rng, idx, idx_step)
+        self.max_t = max_t or int(math.log2(pool.shape[3]))
+        self.x_tm1 = torch.empty_like(self.x_t)
+        self.target = target
+
+    def source(self):
+        return ops.BatchSource.cold(self.pool, SITE_DATA, self.max_t, self.x_tm1, self.idx, draw_idx=self.draw,
+                                    target_x0=self.target == "x0", idx_step=self.idx_step)
+
+
+class GaussianBatcher(_Batcher):
+    """Gaussian DDIM batches: (q_sample(x0, t, eps), x0, t), t ~ U{0..T-1} (``DiffusionDataset``,
+    diffusion_loader.py:24-58).  One launch (:func:`ops.gauss_batch`: pool draw + noise +
+    q_sample), or none at all when the engine fuses the draw into its patch-embedding launch
+    (:meth:`fused_spec`, same values)."""
 
     def __init__(self, pool: torch.Tensor, batch: int, rng: torch.Tensor, total_steps: int = 2000,
                  idx: torch.Tensor | None = None, idx_step=None):
-        self.pool = pool
-        B, (C, H, W) = batch, pool.shape[1:]
-        dev = pool.device
+        super().__init__(pool, batch, rng, idx, idx_step)
         self.T = total_steps
-        self.x_t = torch.empty(B, C, H, W, device=dev)
-        self.x0 = torch.empty(B, C, H, W, device=dev)
-        self.t = torch.empty(B, dtype=torch.int64, device=dev)
-        self.draw = idx is None
-        self.idx = torch.empty(B, dtype=torch.int64, device=dev) if idx is None else idx
-        self.rng = rng
-        self.B = B
-        self.idx_step = idx_step
+        self.x0 = torch.empty_like(self.x_t)
+        self.B = batch
 
-    def fused_spec(self):
-        """``((x_t, x0, t), spec)`` for :func:`ops.patch_embed_cold_fwd` (Gaussian mode)."""
-        cold = (self.pool, SITE_DATA, 1, self.draw, True, self.x0, self.idx, False, self.T, SITE_NOISE, self.idx_step)
-        return (self.x_t, self.x0, self.t), cold
-
-    def __call__(self):
-        ops.gauss_batch(self.pool, self.rng, SITE_DATA, SITE_NOISE, self.T, self.x_t, self.x0, self.t, self.idx,
-                        self.draw, idx_step=self.idx_step)
-        return self.x_t, self.x0, self.t
+    def source(self):
+        return ops.BatchSource.gaussian(self.pool, SITE_DATA, SITE_NOISE, self.T, self.x0, self.idx,
+                                        draw_idx=self.draw, idx_step=self.idx_step)
 
 
 def make_batcher(kind: str, pool: torch.Tensor, batch: int, rng: torch.Tensor, total_steps: int = 2000,

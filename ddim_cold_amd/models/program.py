@@ -372,8 +372,9 @@ class ViTProgram:
         GEMM: ``img`` (the current x_t) is updated in place and returned.  ``loss =
         (target, beta)`` (LayerNorm-folded program only, see :meth:`supports_fused_loss`)
         returns ``(loss_parts, dtok)`` from :func:`ops.head_loss` instead of the image.
-        ``cold`` (LayerNorm-folded program only): the cold batch draw fused into the
-        patch embedding (:func:`ops.patch_embed_cold_fwd`); ``img``/``t`` are its outputs."""
+        ``cold`` (LayerNorm-folded program only): an :class:`ops.BatchSource` whose draw is
+        fused into the patch embedding (:func:`ops.patch_embed_cold_fwd`); ``img``/``t`` are
+        its outputs."""
         if P.folded and fold_width_ok(self.cfg.dim):
             return self._forward_folded(P, img, t, rng, training, save, head_step, loss, cold)
         if loss is not None or cold is not None:

@@ -22,7 +22,7 @@ __all__ = [
     "linear_residual_fwd", "linear_gelu_fwd", "head_fwd", "smooth_l1_fwd_bwd", "img_to_tokgrad",
     "linear_dgrad", "linear_dgrad_gelu", "linear_wgrad", "layernorm_bwd", "attn_bwd", "embed_bwd",
     "sqnorm", "adamw_step", "weight_ema_decay", "advance_counters", "ddim_step", "ddim_step_", "randn_", "q_sample",
-    "pixelate_pair", "cold_batch", "gauss_batch", "head_step_rows_", "cold_step_", "cold_step_rows_",
+    "pixelate_pair", "cold_batch", "gauss_batch", "batch_draw", "BatchSource", "head_step_rows_", "cold_step_", "cold_step_rows_",
     "image_to_rows", "rows_to_image", "embed_weight_rows", "patch_embed_cold_fwd", "ln_fold_", "SITE_STEP_NOISE",
     "HEAD_DDIM", "HEAD_CLAMP", "HEAD_DDIM_EACH", "HEAD_ETA", "HEAD_ETA_EACH",
 ]
@@ -56,33 +56,22 @@ def patch_embed_fwd(img, t, w_pe, b_pe, cls, pos, temb, rng, site: int, p: float
 
 def patch_embed_cold_fwd(cold, img, t, w_pe, b_pe, cls, pos, temb, rng, site: int, p: float, patch: int,
                          ln_st=None, xb_out=None, target_rows: bool = False):
-    """:func:`cold_batch` fused into :func:`patch_embed_fwd` (one launch fewer per
-    training step): ``cold = (pool, data_site, max_t, draw_idx, target_x0, target,
-    idx, write_xt)``; the patch rows are pixelated straight from the pool, ``target``,
-    ``t`` and (if ``draw_idx``) ``idx`` are written, ``img`` (x_t) only if ``write_xt``.
-    Same values as ``cold_batch`` then ``patch_embed_fwd``.  Two optional trailing
-    entries ``(gauss_T, noise_site)`` with ``gauss_T > 0`` select the Gaussian DDIM
-    batch instead (same values as :func:`gauss_batch` then ``patch_embed_fwd``).
-    ``target_rows``: the target is written as patch rows in the head's output column
-    order (:func:`image_to_rows`) into the same buffer, for :func:`head_loss` with
-    ``target_rows``.  An 11th entry ``idx_step = (ctr, off)`` (or None): ``idx`` is a
-    stepped table read at row ``ctr[0] % rows`` (see :func:`stepped_idx`)."""
-    pool, dsite, max_t, draw, tx0, target, idx, write_xt = cold[:8]
-    gT, nsite = (int(cold[8]), int(cold[9])) if len(cold) > 8 else (0, 0)
-    step = cold[10] if len(cold) > 10 else None
+    """The draw of the :class:`BatchSource` ``cold`` (a plain tuple of its order is taken
+    too) fused into :func:`patch_embed_fwd`, one launch fewer per training step: the
+    patch rows come straight from the pool, ``img`` (x_t) and ``t`` are outputs.  Same
+    values as :func:`batch_draw` then ``patch_embed_fwd``.  ``target_rows``: the target is
+    written as patch rows in the head's output column order (:func:`image_to_rows`) into
+    the same buffer, for :func:`head_loss` with ``target_rows``."""
+    src = BatchSource(*cold)
     if _hip(img):
-        ctr, off = step if step is not None else (None, 0)
-        return _ops().patch_embed_cold_fwd(pool, int(dsite), int(max_t), bool(draw), bool(tx0), img, target, t, idx,
-                                           bool(write_xt), w_pe, b_pe, cls, pos, temb, rng, site, float(p), patch,
-                                           ln_st, xb_out, gT, nsite, bool(target_rows), ctr, int(off))
-    if gT > 0:
-        gauss_batch(pool, rng, dsite, nsite, gT, img, target, t, idx, draw, idx_step=step)
-    else:
-        cold_batch(pool, rng, dsite, img, target, t, idx, max_t, draw, idx_step=step)
-        if tx0:
-            torch.index_select(pool, 0, stepped_idx(idx, step, img.shape[0]), out=target)
+        ctr, off = src.idx_step if src.idx_step is not None else (None, 0)
+        return _ops().patch_embed_cold_fwd(src.pool, int(src.site), int(src.max_t), bool(src.draw_idx),
+                                           bool(src.target_x0), img, src.target, t, src.idx, bool(src.write_xt), w_pe,
+                                           b_pe, cls, pos, temb, rng, site, float(p), patch, ln_st, xb_out,
+                                           int(src.gauss_T), int(src.noise_site), bool(target_rows), ctr, int(off))
+    batch_draw(src, rng, img, t)
     if target_rows:
-        target.copy_(image_to_rows(target.clone(), patch).reshape(target.shape))
+        src.target.copy_(image_to_rows(src.target.clone(), patch).reshape(src.target.shape))
     return patch_embed_fwd(img, t, w_pe, b_pe, cls, pos, temb, rng, site, p, patch, ln_st, xb_out)
 
 
@@ -477,6 +466,47 @@ class EmbedGrads(NamedTuple):
     dtemb: torch.Tensor
     owners: int
     ln: Optional[LnFinal] = None
+
+
+class BatchSource(NamedTuple):
+    """A training batch source, from the batcher (``data.synthetic``) to the kernels
+    (``ColdSrc`` in csrc/kernels.h): the draw of one batch (x_t, target, t), either fused into
+    the patch embedding (:func:`patch_embed_cold_fwd`) or on its own (:func:`batch_draw`).
+
+    ``pool`` [n,C,H,W]: the images drawn from.  ``site``: the RNG site of the pool index and of
+    t.  ``max_t``: t ~ U{1..max_t} and x_t = the pool image pixelated by 2^t (cold
+    diffusion).  ``draw_idx``: the pool indices are drawn and written to ``idx``; else ``idx``
+    holds them.  ``target_x0``: the target is the pool image x0, else x_{t-1}.  ``target``
+    [B,C,H,W] and ``idx`` [B]: written (idx only if drawn).  ``write_xt``: the fused draw
+    writes the x_t image as well as its patch rows (the draw on its own always does).
+    ``gauss_T`` > 0: the Gaussian DDIM batch instead -- t ~ U{0..gauss_T-1}, x_t =
+    q_sample(x0, t, eps) with eps = :func:`randn_` at ``noise_site``, target x0 (``max_t``
+    unused).  ``idx_step = (ctr, off)``: ``idx`` is a stepped table read at row ``ctr[0] %
+    rows``, elements ``off .. off+B`` (:func:`stepped_idx`).
+
+    Field order is the op's positional order: a plain tuple of the first 8, 10 or all 11
+    entries is taken wherever a ``BatchSource`` is."""
+    pool: torch.Tensor
+    site: int
+    max_t: int
+    draw_idx: bool
+    target_x0: bool
+    target: torch.Tensor
+    idx: torch.Tensor
+    write_xt: bool
+    gauss_T: int = 0
+    noise_site: int = 0
+    idx_step: Optional[tuple] = None
+
+    @classmethod
+    def cold(cls, pool, site: int, max_t: int, target, idx, draw_idx: bool = True, target_x0: bool = False,
+             write_xt: bool = False, idx_step=None):
+        return cls(pool, site, max_t, draw_idx, target_x0, target, idx, write_xt, 0, 0, idx_step)
+
+    @classmethod
+    def gaussian(cls, pool, site: int, noise_site: int, total_steps: int, x0, idx, draw_idx: bool = True,
+                 write_xt: bool = False, idx_step=None):
+        return cls(pool, site, 1, draw_idx, True, x0, idx, write_xt, total_steps, noise_site, idx_step)
 
 
 class StepTail(NamedTuple):
@@ -883,3 +913,18 @@ def cold_batch(pool, rng, site: int, x_t, x_tm1, t, idx_ws, max_t: int, draw_idx
     a, c = pixelate_pair(pool, idx_ws, t, B)
     x_t.copy_(a)
     x_tm1.copy_(c)
+
+
+def batch_draw(src, rng, x_t, t):
+    """The draw of a :class:`BatchSource` on its own (not fused into the patch embedding):
+    :func:`gauss_batch` when ``src.gauss_T > 0``, else :func:`cold_batch`, whose x_{t-1}
+    target the pool images replace when ``src.target_x0``.  Writes ``x_t``, ``t``,
+    ``src.target`` and (if drawn) ``src.idx``."""
+    src = BatchSource(*src)
+    if src.gauss_T > 0:
+        gauss_batch(src.pool, rng, src.site, src.noise_site, src.gauss_T, x_t, src.target, t, src.idx, src.draw_idx,
+                    idx_step=src.idx_step)
+        return
+    cold_batch(src.pool, rng, src.site, x_t, src.target, t, src.idx, src.max_t, src.draw_idx, idx_step=src.idx_step)
+    if src.target_x0:
+        torch.index_select(src.pool, 0, stepped_idx(src.idx, src.idx_step, x_t.shape[0]), out=src.target)

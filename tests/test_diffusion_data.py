@@ -294,3 +294,68 @@ def test_stepped_index_table_cpu():
             a = make_batcher(kind, pool, 3, rng, idx=table, idx_step=(ctr[1:], 3 * j))()
             b = make_batcher(kind, pool, 3, rng, idx=want.clone())()
             assert all(torch.equal(u, v) for u, v in zip(a, b)), kind
+
+
+@pytest.mark.parametrize("mode", ["drawn", "idx", "table+0", "table+3"])
+@pytest.mark.parametrize("kind", ["cold", "cold_x0", "gaussian"])
+def test_batch_source_is_the_plain_tuple_and_draws_the_same(kind, mode):
+    """A batcher's ``fused_spec()[1]`` is an ``ops.BatchSource`` that equals, entry by entry, the
+    plain 11-tuple written out here (data site 3, noise site 4, max_t = log2 16 = 4);
+    ``ops.batch_draw`` of it is the batcher's own call bit for bit; and ``patch_embed_cold_fwd``
+    takes it and every plain tuple cut after 8 / 10 / 11 entries that loses nothing but defaults."""
+    from ddim_cold_amd.data.synthetic import make_batcher
+    B, patch, D, T = 3, 4, 32, 50
+    pool = synthetic_pool(8, size=(16, 16))
+    g = torch.Generator().manual_seed(5)
+    table = torch.randint(0, 8, (3, 2, 3), generator=g)
+    ctr = torch.tensor([0, 5])
+    rng = torch.tensor([7, 2])
+    idx, step = {"drawn": (None, None), "idx": (torch.tensor([6, 0, 3]), None),
+                 "table+0": (table, (ctr[1:], 0)), "table+3": (table, (ctr[1:], 3))}[mode]
+    b = make_batcher(kind, pool, B, rng, total_steps=T, idx=idx, idx_step=step)
+    bufs, spec = b.fused_spec()
+    draw = mode == "drawn"
+    tgt = b.x0 if kind == "gaussian" else b.x_tm1
+    want = {"cold": (pool, 3, 4, draw, False, tgt, b.idx, False, 0, 0, step),
+            "cold_x0": (pool, 3, 4, draw, True, tgt, b.idx, False, 0, 0, step),
+            "gaussian": (pool, 3, 1, draw, True, tgt, b.idx, False, 50, 4, step)}[kind]
+    assert isinstance(spec, ops.BatchSource) and len(spec) == 11
+    assert spec._fields == ("pool", "site", "max_t", "draw_idx", "target_x0", "target", "idx", "write_xt", "gauss_T",
+                            "noise_site", "idx_step")
+    for name, got, exp in zip(spec._fields, spec, want):
+        same = got is exp if isinstance(exp, (torch.Tensor, tuple)) else (type(got) is type(exp) and got == exp)
+        assert same, (name, got, exp)
+    assert bufs[0] is b.x_t and bufs[1] is spec.target and bufs[2] is b.t
+    assert draw or b.idx is idx
+
+    # the unfused draw: ops.batch_draw into fresh buffers == the batcher's call
+    x_t, target, t = (u.clone() for u in b())
+    fresh = spec._replace(target=torch.zeros_like(target), idx=torch.zeros_like(b.idx) if draw else spec.idx)
+    x2, t2 = torch.zeros_like(x_t), torch.zeros_like(t)
+    ops.batch_draw(fresh, rng, x2, t2)
+    assert torch.equal(x2, x_t) and torch.equal(t2, t) and torch.equal(fresh.target, target)
+    assert torch.equal(fresh.idx, b.idx)
+    if step is not None:
+        assert torch.equal(ops.stepped_idx(table, step, B), table[5 % 3].reshape(-1)[step[1]:step[1] + B])
+
+    # the fused op: the BatchSource and the plain tuples give the same outputs
+    N = (16 // patch) ** 2 + 1
+    w = (torch.randn(D, 3 * patch * patch, generator=g) * 0.1).to(torch.bfloat16)
+    args = (w, torch.randn(D, generator=g), torch.randn(D, generator=g), torch.randn(N * D, generator=g),
+            torch.randn(T, D, generator=g), rng, 1, 0.1, patch)
+
+    def run(cold, target_rows):
+        img, tt = torch.zeros_like(x_t), torch.zeros_like(t)
+        st, xb = torch.zeros(B * N, D // 32, 2), torch.zeros(B * N, D, dtype=torch.bfloat16)
+        spec.target.zero_()
+        x, p = ops.patch_embed_cold_fwd(cold, img, tt, *args, ln_st=st, xb_out=xb, target_rows=target_rows)
+        return x, p, img, tt, spec.target.clone(), st, xb
+
+    for target_rows in (False, True):
+        base = run(spec, target_rows)
+        assert torch.equal(base[2], x_t) and torch.equal(base[3], t)
+        assert torch.equal(base[4], ops.image_to_rows(target, patch).reshape(target.shape) if target_rows else target)
+        cuts = [n for n in (8, 10, 11) if tuple(spec[n:]) == (0, 0, None)[n - 8:]]
+        assert cuts[0] == (11 if step is not None else 10 if kind == "gaussian" else 8)
+        for n in cuts:
+            assert all(torch.equal(u, v) for u, v in zip(run(tuple(spec)[:n], target_rows), base)), n

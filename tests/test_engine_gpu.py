@@ -387,6 +387,117 @@ def test_patch_embed_cold_stepped_table_matches_explicit():
     assert all(torch.equal(u, v) for u, v in zip(a, b))
 
 
+class _BatchOps:
+    """The three batch-draw ops (the fused one in its cold and its Gaussian mode) on one small
+    batch source (B = 2, 3 x 16 x 16, patch 4, a pool of 4, 7 time-embedding rows), each called
+    through one ``call(op, **overrides)``; every buffer an op could write starts at -7."""
+    OPS = ("cold_batch", "gauss_batch", "fused cold", "fused gaussian")
+    B, D, T, PATCH = 2, 128, 7, 4
+
+    def __init__(self, dev="cuda"):
+        from ddim_cold_amd.data.synthetic import synthetic_pool
+        g = torch.Generator().manual_seed(0)
+        N = (16 // self.PATCH) ** 2 + 1
+        self.dev = dev
+        self.rng = torch.tensor([11, 5], dtype=torch.int64, device=dev)
+        self.pool = synthetic_pool(4, size=(16, 16), seed=2, device=dev)
+        self.table = torch.randint(0, 4, (3, 2, 2), generator=g).to(dev)  # rows of 4: two batches of B
+        self.ctr = torch.tensor([4], dtype=torch.int64, device=dev)
+        w = (torch.randn(self.D, 3 * self.PATCH ** 2, generator=g) * 0.1).to(torch.bfloat16)
+        self.embed = tuple(x.to(dev) for x in (w, torch.randn(self.D, generator=g), torch.randn(self.D, generator=g),
+                                               torch.randn(N * self.D, generator=g),
+                                               torch.randn(self.T, self.D, generator=g)))
+        self.made = []
+
+    def buf(self, *shape, dtype=torch.float32):
+        self.made.append(torch.full(shape, -7, dtype=dtype, device=self.dev))
+        return self.made[-1]
+
+    def call(self, op, **over):
+        from ddim_cold_amd import ops
+        B = self.B
+        d = dict(dict(pool=self.pool, img=None, target=None, t=None, idx=None, draw=True, step=None, max_t=4,
+                      gauss_T=self.T), **over)
+        for k, shape in (("img", (B, 3, 16, 16)), ("target", (B, 3, 16, 16)), ("t", (B,)), ("idx", (B,))):
+            if d[k] is None:
+                d[k] = self.buf(*shape, dtype=torch.int64 if k in ("t", "idx") else torch.float32)
+        if op == "cold_batch":
+            ops.cold_batch(d["pool"], self.rng, 3, d["img"], d["target"], d["t"], d["idx"], d["max_t"], d["draw"],
+                           idx_step=d["step"])
+        elif op == "gauss_batch":
+            ops.gauss_batch(d["pool"], self.rng, 3, 4, d["gauss_T"], d["img"], d["target"], d["t"], d["idx"],
+                            d["draw"], idx_step=d["step"])
+        else:
+            gT = d["gauss_T"] if op == "fused gaussian" else 0
+            cold = (d["pool"], 3, d["max_t"], d["draw"], gT > 0, d["target"], d["idx"], True, gT, 4, d["step"])
+            d["x"], d["patches"] = ops.patch_embed_cold_fwd(cold, d["img"], d["t"], *self.embed, self.rng, 1, 0.1,
+                                                            self.PATCH)
+        return d
+
+
+@pytest.mark.gpu
+def test_batch_ops_refuse_bad_sources_before_launching():
+    """cold_batch, gauss_batch and patch_embed_cold_fwd share one host-side check of the batch
+    source: each refuses a mis-shaped pool / target / t / image, a stepped table read past its
+    row or drawn into, a max_t whose 2^max_t block cannot exist (cold), a gauss_T past the
+    time-embedding rows (fused), and nothing was written.  After the refusals a valid call of
+    each op still gives its CPU fallback's batch: bit for bit where the arithmetic is exact
+    (indices, t, gathered and pixelated images, bf16 patch rows); the Gaussian x_t to the float
+    rounding of the fast log / sincos, as in test_gauss_batch_matches_reference_and_fused_embed;
+    the cold mode's tokens against patch_embed_fwd on the same device, bit for bit."""
+    from ddim_cold_amd import ops
+    s = _BatchOps()
+    B = s.B
+    every = {
+        "pool C": lambda: dict(pool=s.pool[:, :2].contiguous()),
+        "pool H": lambda: dict(pool=s.pool[:, :, :8].contiguous()),
+        "pool W": lambda: dict(pool=s.pool[:, :, :, :8].contiguous()),
+        "target shape": lambda: dict(target=s.buf(B, 3, 16, 8)),
+        "t of B + 1": lambda: dict(t=s.buf(B + 1, dtype=torch.int64)),
+        "3-D image": lambda: dict(img=s.buf(B * 3, 16, 16)),
+        "table row overrun": lambda: dict(idx=s.table, draw=False, step=(s.ctr, 3)),
+        "table drawn into": lambda: dict(idx=s.table, draw=True, step=(s.ctr, 0)),
+    }
+    cases = [(op, name, over) for op in s.OPS for name, over in every.items()]
+    cases += [(op, f"max_t={m}", lambda m=m: dict(max_t=m)) for op in ("cold_batch", "fused cold") for m in (0, 40)]
+    cases += [("fused gaussian", "gauss_T past temb", lambda: dict(gauss_T=s.T + 1))]
+    table0 = s.table.clone()
+    for op, name, over in cases:
+        with pytest.raises(RuntimeError):
+            s.call(op, **over())
+            pytest.fail(f"{op} accepted: {name}")
+    torch.cuda.synchronize()
+    assert all(bool((b == -7).all()) for b in s.made) and torch.equal(s.table, table0)
+
+    c = _BatchOps("cpu")
+    for op in s.OPS:
+        for stepped in (False, True):  # drawn indices / row 4 % 3 of the table, its second batch
+            a, b = (o.call(op, **(dict(idx=o.table, draw=False, step=(o.ctr, 2)) if stepped else {})) for o in (s, c))
+            torch.cuda.synchronize()
+            assert torch.equal(s.table, table0)
+            for k in ("t", "target") + (() if stepped else ("idx",)):
+                assert torch.equal(a[k].cpu(), b[k]), (op, k)
+            if "gauss" in op:
+                assert (a["img"].cpu() - b["img"]).abs().max().item() < 2e-4, op
+            else:
+                assert torch.equal(a["img"].cpu(), b["img"]), op
+            if op == "fused cold":
+                x_ref, p_ref = ops.patch_embed_fwd(a["img"], a["t"], *s.embed, s.rng, 1, 0.1, s.PATCH)
+                assert torch.equal(a["x"], x_ref) and torch.equal(a["patches"], p_ref)
+                assert torch.equal(a["patches"].cpu(), b["patches"])
+
+
+@pytest.mark.gpu
+@pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs two visible devices")
+def test_batch_ops_refuse_an_operand_on_another_device():
+    """t on another device than the image: refused on the host (a pointer to another device's
+    memory in a hand-written kernel is a GPU fault)."""
+    s = _BatchOps()
+    for op in s.OPS:
+        with pytest.raises(RuntimeError):
+            s.call(op, t=torch.full((s.B,), -7, dtype=torch.int64, device="cuda:1"))
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("dataset", ["cold", "gauss"])
 def test_embed_in_wgrad_launch_matches_separate_launch(monkeypatch, dataset):

@@ -45,7 +45,7 @@ def set_switch(name: str, on: bool):
 
 
 def case(label, steps=3, off=None, fold=True, name="vit_tiny", model_kw=None, size=64, B=8, gauss=False, layout=None,
-         **cfg):
+         target="prev", table=False, **cfg):
     for s in SWITCHES:
         set_switch(s, s != off)
     program.FOLD_LN = fold
@@ -59,7 +59,12 @@ def case(label, steps=3, off=None, fold=True, name="vit_tiny", model_kw=None, si
         if layout is not None:
             eng.apply_layout(layout)
     pool = synthetic_pool(64, size=(size, size), seed=1, device=dev)
-    eng.set_batch_fn(GaussianBatcher(pool, B, eng.rng, 2000) if gauss else ColdBatcher(pool, B, eng.rng))
+    src = {}
+    if table:  # the trainer's epoch table [steps, micro-batch, B], read at the device step counter (2 rows: it wraps)
+        rows = torch.randint(0, 64, (2, 1, B), generator=torch.Generator().manual_seed(2)).to(dev)
+        src = dict(idx=rows, idx_step=(eng.step_ctr[1:2], 0))
+    eng.set_batch_fn(GaussianBatcher(pool, B, eng.rng, 2000, **src) if gauss
+                     else ColdBatcher(pool, B, eng.rng, target=target, **src))
     eng.train_steps(steps)
     if cuda:
         torch.cuda.synchronize()
@@ -88,6 +93,9 @@ CASES = {
     "FOLD_LN off": dict(fold=False, **G),
     "weight_ema=0.99": dict(weight_ema=0.99, **G),
     "gaussian temb_rows=None": dict(gauss=True, temb_rows=None, **G),
+    "cold_x0": dict(target="x0", **G),
+    "cold stepped table": dict(table=True, **G),
+    "gaussian stepped table": dict(gauss=True, table=True, temb_rows=None, **G),
     "frozen time embedding": dict(model_kw=dict(timestep_embedding="sinusoidal"), **G),
     "vit_small_200 depth 2": dict(name="vit_small_200", model_kw=dict(depth=2), size=200, B=2, **G),
     "dp overlap-2": dict(layout="overlap-2", **DP),
