@@ -42,6 +42,10 @@ import dataclasses
 import math
 from typing import Dict, List, Optional, Sequence, Tuple
 
+# (runs train/__init__, i.e. imports the engine: no cycle as long as engine.py imports this
+# module inside the functions that use it, as it does, and never at its top)
+from ..train.layout import bucket_groups
+
 LINK_GBS = 153.0  # one xGMI link, each direction (MI355X)
 LINKS_PER_GPU = 7
 
@@ -140,21 +144,12 @@ def vit_step_profile(depth: int, dim: int, hidden: int, batch_tokens: int, other
 
 
 def bucket_plan(prof: StepProfile, bucket_blocks: int, embed_bucket: bool = True) -> List[Tuple[int, float]]:
-    """(blocks, wire bytes) per bucket in backward order -- the layout
-    ``TrainEngine._build_buckets`` makes: ``bucket_blocks`` blocks per bucket from
-    the last block down (the head with the first of them), the embeddings + every
-    LayerNorm (``embed_bytes``) in a last
-    bucket of their own when ``embed_bucket`` else with block 0's bucket."""
-    out = []
-    left = prof.depth
-    while left > 0:
-        k = min(bucket_blocks, left)
-        left -= k
-        out.append([k, k * prof.block_bytes + (prof.head_bytes if not out else 0.0)])
-    if embed_bucket:
-        out.append([0, prof.embed_bytes])
-    else:
-        out[-1][1] += prof.embed_bytes
+    """(blocks, wire bytes) per bucket in backward order, the buckets being the engine's
+    (``train.layout.bucket_groups``): the head goes with the first of them, the
+    embeddings + every LayerNorm (``embed_bytes``) with the last."""
+    out = [[len(g), len(g) * prof.block_bytes] for g in bucket_groups(prof.depth, bucket_blocks, embed_bucket)]
+    out[0][1] += prof.head_bytes
+    out[-1][1] += prof.embed_bytes
     return [(k, b) for k, b in out]
 
 

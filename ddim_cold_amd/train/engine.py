@@ -53,8 +53,8 @@ import torch.distributed as dist
 from .. import ops
 from ..models import program as _program
 from ..models.program import BackwardPlan, LnFold, ModelTensors, ViTProgram, collect, is_matrix_param
+from .layout import ArenaLayout, BucketLayout, arena_layout, bucket_layout
 
-ALIGN = 64  # elements (256 B fp32)
 # Step graphs are captured in thread-local mode: other threads' HIP calls during a
 # capture (ProcessGroupNCCL's watchdog polling the events of eager collectives)
 # neither invalidate the capture nor fail in that thread.  In the default global
@@ -221,10 +221,6 @@ class EngineConfig:
     weight_ema_warmup: bool = True
 
 
-def _align(n: int) -> int:
-    return (n + ALIGN - 1) // ALIGN * ALIGN
-
-
 @dataclass(frozen=True)
 class Switches:
     """The module switches above, as read when a :class:`StepPlan` is built."""
@@ -301,9 +297,7 @@ class TrainEngine:
                                    float(cfg.t_max), cfg.eta_min], dtype=torch.float32, device=dev)
         # grad-norm partials (sqnorm, or the fused weight-gradient launch: one per 64x64
         # output tile + tail workgroups; the 2-D parameter count bounds the tiles)
-        tiles = sum(-(-p.shape[0] // 64) * -(-(p[0].numel()) // 64) for p in model.parameters() if p.dim() >= 2)
-        self._sq_tiles = tiles
-        self.sqnorm = torch.zeros(ops.sq_parts_size(tiles), dtype=torch.float32, device=dev)
+        self.sqnorm = torch.zeros(ops.sq_parts_size(self.layout.sq_tiles), dtype=torch.float32, device=dev)
         # tickets of the weight-gradient launches' K-split tails: this engine's own, allocated
         # here (never inside a capture) and shared by its graphs, whose launches one stream orders
         self.wgrad_tickets = ops.wgrad_tickets(dev) if self.is_cuda else None
@@ -358,7 +352,7 @@ class TrainEngine:
         self._ema_scope = False   # inside ema_weights(): flat_p holds the EMA
         if cfg.weight_ema > 0:
             self.flat_e = self.flat_p.clone()
-            self.opt_e = self.flat_e[:self.train_hi]
+            self.opt_e = self.flat_e[:self.layout.train_hi]
         model._engine = self
 
     def _comm_stream(self):
@@ -472,7 +466,7 @@ class TrainEngine:
         same parameters (no broadcast here)."""
         if not (self.segmented and self.is_cuda):
             raise ValueError("attach_comm needs a GPU engine built with force_segments=True")
-        if self.temb_bucket is not None and not hasattr(comm, "all_gather_"):
+        if self.bucketing.temb_bucket is not None and not hasattr(comm, "all_gather_"):
             raise ValueError(f"{type(comm).__name__} has no all_gather_, which this engine's sparse time-embedding "
                              "gradient exchange needs (Gaussian diffusion: temb_rows=None); build the engine "
                              "with temb_rows or temb_sparse=False")
@@ -492,85 +486,44 @@ class TrainEngine:
 
     # ------------------------------------------------------------------ arenas
     def _build_arenas(self):
+        """Allocate the arenas that :attr:`layout` (``train/layout.py``: the ordering policy
+        and the alignment) describes and rebind the model's parameters and gradients as
+        views of them; then everything else that holds arena views."""
         named = list(self.model.named_parameters())
-        self.names = [n for n, _ in named]
-        self.offsets: Dict[str, Tuple[int, int]] = {}
-        # LayerNorm weight+bias are packed back to back (one [2D] range for the
-        # replica finalize); every other tensor starts 256-B aligned.
-        ln_prefixes = {n[: -len(".weight")] for n, p in named
-                       if n.endswith(".weight") and p.dim() == 1 and (n.startswith("norm") or ".norm" in n)}
-        # arena order: embeddings, then EVERY LayerNorm, then the blocks' Linear
-        # weights, then the head.  The LayerNorm gradients are finalised once, in the
-        # embedding-backward launch (their dgamma/dbeta replicas are only complete
-        # then); placed here they fall in the last all-reduce bucket, so data
-        # parallel needs no replica finalize launch per bucket either.
-        # Frozen tensors (requires_grad=False, e.g. the fixed sinusoidal time table,
-        # ViT_draft2drawing.py:140-156) go last, past ``train_hi``: the norm, AdamW and
-        # the all-reduce buckets cover [0, train_hi) only, so a frozen tensor gets no
-        # weight decay, no moments and no optimizer state (torch.optim skips a
-        # parameter whose .grad is None).
-        self.frozen = {n for n, p in named if not p.requires_grad}
-
-        def group(n):
-            if n in self.frozen:
-                return 4
-            if n.rsplit(".", 1)[0] in ln_prefixes:
-                return 1
-            if n.startswith("blocks."):
-                return 2
-            return 3 if n.startswith("head.") else 0
-        layout = sorted(named, key=lambda np_: group(np_[0]))  # stable: original order within a group
-        off = 0
-        self.train_hi = None
-        for n, p in layout:
-            ln_bias = n.endswith(".bias") and n[: -len(".bias")] in ln_prefixes
-            if not ln_bias:
-                off = _align(off)
-            if n in self.frozen and self.train_hi is None:
-                self.train_hi = off
-            self.offsets[n] = (off, p.numel())
-            off += p.numel()
-        off = _align(off)
-        self.numel = off
-        if self.train_hi is None:
-            self.train_hi = off
-        dev = self.device
-        self.flat_p = torch.zeros(off, dtype=torch.float32, device=dev)
-        self.flat_g = torch.zeros(off, dtype=torch.float32, device=dev)
-        self.flat_m = torch.zeros(off, dtype=torch.float32, device=dev)
-        self.flat_v = torch.zeros(off, dtype=torch.float32, device=dev)
-        self.flat_pb = torch.zeros(off, dtype=torch.bfloat16, device=dev)
-        if self.cfg.grad_wire not in ("fp32", "bf16"):
-            raise ValueError(f"grad_wire must be 'fp32' or 'bf16', got {self.cfg.grad_wire!r}")
-        self.flat_gw = torch.zeros(off, dtype=torch.bfloat16, device=dev) if self.cfg.grad_wire == "bf16" else None
-        views_p, views_g = {}, {}
+        c, cfg, dev = self.prog.cfg, self.cfg, self.device
+        self.layout: ArenaLayout = arena_layout([(n, tuple(p.shape), p.requires_grad) for n, p in named],
+                                                c.depth, c.dim, c.total_steps, cfg.temb_rows, cfg.weight_ema)
+        lay = self.layout
+        self.flat_p = torch.zeros(lay.numel, dtype=torch.float32, device=dev)
+        self.flat_g = torch.zeros(lay.numel, dtype=torch.float32, device=dev)
+        self.flat_m = torch.zeros(lay.numel, dtype=torch.float32, device=dev)
+        self.flat_v = torch.zeros(lay.numel, dtype=torch.float32, device=dev)
+        self.flat_pb = torch.zeros(lay.numel, dtype=torch.bfloat16, device=dev)
+        if cfg.grad_wire not in ("fp32", "bf16"):
+            raise ValueError(f"grad_wire must be 'fp32' or 'bf16', got {cfg.grad_wire!r}")
+        self.flat_gw = torch.zeros(lay.numel, dtype=torch.bfloat16, device=dev) if cfg.grad_wire == "bf16" else None
+        views_g = {}
         for n, p in named:
-            o, k = self.offsets[n]
+            o, k = lay.offsets[n]
             vp = self.flat_p[o:o + k].view_as(p)
             vp.copy_(p.data)
             p.data = vp
-            vg = self.flat_g[o:o + k].view_as(p)
-            p.grad = None if n in self.frozen else vg
-            views_g[n] = vg
+            views_g[n] = self.flat_g[o:o + k].view_as(p)
+            p.grad = None if n in lay.frozen else views_g[n]
         # the optimizer's ranges (frozen tensors excluded)
-        th = self.train_hi
         self.opt_p, self.opt_g, self.opt_m, self.opt_v, self.opt_pb = (
-            t[:th] for t in (self.flat_p, self.flat_g, self.flat_m, self.flat_v, self.flat_pb))
-        c = self.prog.cfg
+            t[:lay.train_hi] for t in (self.flat_p, self.flat_g, self.flat_m, self.flat_v, self.flat_pb))
+        # the bf16 shadows the MFMA GEMMs read; every other parameter is read in fp32
+        shadows = {n: self.flat_pb[o:o + k].view(p.shape)
+                   for n, p in named for o, k in [lay.offsets[n]] if is_matrix_param(n)}
         # LayerNorm fold: gamma-scaled bf16 weights / row sums / folded biases of
         # the QKV, fc1 and head GEMMs, recomputed from the fp32 masters after
         # every optimizer step (inside the step graph)
         # (reads the bf16 shadow the optimizer just wrote: half the bytes of the fp32 masters)
-        self.lnfold = LnFold({n: p.data for n, p in named}, c.depth,
-                             weights={n: self.flat_pb[o:o + k].view(p.shape)
-                                      for n, p in named for o, k in [self.offsets[n]] if is_matrix_param(n)}) \
-            if _program.FOLD_LN else None
+        self.lnfold = LnFold({n: p.data for n, p in named}, c.depth, weights=shadows) if _program.FOLD_LN else None
         self.wt = None
         self._refresh_shadow()
-        for n, p in named:
-            o, k = self.offsets[n]
-            views_p[n] = self.flat_pb[o:o + k].view(p.shape) if is_matrix_param(n) else p.data
-        self.param_tensors: ModelTensors = collect(views_p, c.depth, c.dim)
+        self.param_tensors: ModelTensors = collect({n: shadows.get(n, p.data) for n, p in named}, c.depth, c.dim)
         if self.lnfold is not None:
             self.lnfold.attach(self.param_tensors)
         if self.is_cuda and c.tokens >= TRANSPOSED_DGRAD_MIN_TOKENS:
@@ -581,133 +534,53 @@ class TrainEngine:
         if not c.learn_temb:
             self.grad_tensors.temb = None
         self._temb_t: List[torch.Tensor] = []
-        # gradient arena below this element is accumulated (embeddings: atomics in the
-        # embedding backward); above it every range has a single writer per step
-        self.acc_hi = min(self.offsets[n][0] for n in self.names if n.rsplit(".", 1)[0] in ln_prefixes)
-        # time_embed rows no sample can select (t >= temb_rows: cold diffusion draws
-        # t in 1..log2 W): zero gradient and zero Adam moments for the whole run, so
-        # AdamW reduces to p *= (1 - lr wd).  The optimizer skips them and
-        # accumulates that factor on the device (lazy_decay); materialize_lazy()
-        # applies it before anything reads them (end of train_steps, snapshots,
-        # state dicts).  ~11 % of the ViT-tiny arena.
-        self.lazy = None
-        self.lazy_decay = torch.ones(1, dtype=torch.float32, device=self.device)
+        # the optimizer skips the time_embed rows no sample can select (``layout.lazy``) and
+        # accumulates their weight-decay factor on the device (lazy_decay); materialize_lazy()
+        # applies it before anything reads them (end of train_steps, snapshots, state dicts).
+        # Run state: a resume can turn it off (_check_lazy_moments)
+        self.lazy = lay.lazy
+        self.lazy_decay = torch.ones(1, dtype=torch.float32, device=dev)
         self._lazy_dirty = False
-        rows = self.cfg.temb_rows
-        # (off with a weight EMA: the EMA of those rows has to follow them every step)
-        if (rows is not None and 0 < rows < c.total_steps and "time_embed.weight" in self.offsets
-                and "time_embed.weight" not in self.frozen and not self.cfg.weight_ema > 0):
-            to, tn = self.offsets["time_embed.weight"]
-            lo, hi = (to + rows * c.dim + 3) // 4 * 4, (to + tn) // 4 * 4
-            if hi > lo and hi <= self.train_hi:
-                self.lazy = (lo, hi)
-        # LayerNorm dgamma/dbeta replica workspace in backward order: final norm,
-        # then norm2, norm1 of blocks L-1 .. 0; destinations = grad-arena views
-        # (weight and bias of one LayerNorm are adjacent: one [2D] range).
-        D = c.dim
-        L = c.depth
-        order = ["norm"]
-        for i in range(L - 1, -1, -1):
-            order += [f"blocks.{i}.norm2", f"blocks.{i}.norm1"]
-        self.ln_order = order
-        dsts = []
-        for nm in order:
-            ow, _ = self.offsets[nm + ".weight"]
-            ob, _ = self.offsets[nm + ".bias"]
-            assert ob == ow + D, "LayerNorm weight/bias must be adjacent in the arena"
-            dsts.append(self.flat_g[ow:ow + 2 * D])
-        self.ln_dsts = dsts
+        # LayerNorm dgamma/dbeta replica destinations, in ``layout.ln_order``: the grad-arena
+        # range of each one's weight + bias
+        self.ln_dsts = [self.flat_g[o:o + 2 * c.dim] for o in lay.ln_offs]
         # workspace rows depend on the backward's row count (ops.ln_ws_rows): allocated by
-        # _ensure_ln_ws at the first step of a batch size (eager, never inside a capture)
+        # _ensure_batch_buffers at the first step of a batch size (eager, never inside a capture)
         self.ln_ws = None
         self.ln_R = 0
-        self.ln_ptrs = torch.tensor([t.data_ptr() for t in dsts], dtype=torch.int64, device=dev) \
-            if dev.type == "cuda" else None
-        self._ln_prefixes = ln_prefixes
+        self.ln_ptrs = torch.tensor([t.data_ptr() for t in self.ln_dsts], dtype=torch.int64, device=dev) \
+            if self.is_cuda else None
         self._build_buckets()
+
+    def _build_buckets(self):
+        """The gradient-exchange layout of ``cfg.bucket_blocks`` / ``cfg.embed_bucket``
+        (re-run by :meth:`set_comm_layout`)."""
+        sparse = self.cfg.temb_sparse and self.segmented and self.grad_tensors.temb is not None
+        self.bucketing: BucketLayout = bucket_layout(self.layout, self.cfg.bucket_blocks, self.cfg.embed_bucket, sparse)
 
     def _ensure_batch_buffers(self, B: int):
         """Buffers sized by the batch: the LayerNorm dgamma/dbeta slot workspaces
         ([2L+1, ops.ln_ws_rows(B N), 2D]) and room in the grad-norm partials for the
         embedding workgroups of the weight-gradient launch (FUSE_EMBED_WGRAD)."""
-        c = self.prog.cfg
+        c, n_ln = self.prog.cfg, len(self.layout.ln_order)
         D, M = c.dim, B * c.tokens
         rows = ops.ln_ws_rows(M)
-        nparts = ops.sq_parts_size(self._sq_tiles + ops.wgrad_embed_slots(
-            B, c.tokens, D, self._emb_owners(B), len(self.ln_order), 2 * D, M))
+        nparts = ops.sq_parts_size(self.layout.sq_tiles + ops.wgrad_embed_slots(
+            B, c.tokens, D, self._emb_owners(B), n_ln, 2 * D, M))
         if (self.ln_ws is not None and self.ln_ws.shape[1] == rows and self.sqnorm.numel() >= nparts):
             return
         if self.is_cuda and torch.cuda.is_current_stream_capturing():
             raise RuntimeError("the batch size changed inside a graph capture (LayerNorm workspace)")
         self._plans.clear()  # they hold views of the buffers replaced here
-        self.ln_ws = torch.zeros(len(self.ln_order), rows, 2 * D, dtype=torch.float32, device=self.device)
+        self.ln_ws = torch.zeros(n_ln, rows, 2 * D, dtype=torch.float32, device=self.device)
         self.ln_R = rows
         if self.sqnorm.numel() < nparts:
             self.sqnorm = torch.zeros(nparts, dtype=torch.float32, device=self.device)
-
-    def _ln_offs(self):
-        """Arena offsets (elements, from the optimizer's gradient view) of the LayerNorm
-        gradient ranges, in ``ln_order``."""
-        base = self.opt_g.data_ptr()
-        return [(d.data_ptr() - base) // 4 for d in self.ln_dsts]
 
     def _emb_owners(self, B: int) -> int:
         """Distinct timesteps a batch of ``B`` can hold (time-embedding gradient rows)."""
         rows = self.cfg.temb_rows
         return max(1, min(B, rows if rows is not None else self.prog.cfg.total_steps))
-
-    def _build_buckets(self):
-        """All-reduce bucket layout from ``cfg.bucket_blocks`` / ``cfg.embed_bucket``
-        (re-run by :meth:`set_comm_layout`)."""
-        c = self.prog.cfg
-        # all-reduce buckets: contiguous arena ranges, boundaries after block groups (backward order)
-        L = c.depth
-        # a block's arena range starts at its first Linear weight (LayerNorms live
-        # with the embeddings, see the layout above)
-        starts = [min(self.offsets[n][0] for n in self.names if n.startswith(f"blocks.{i}.")
-                      and n.rsplit(".", 1)[0] not in self._ln_prefixes) for i in range(L)]
-        bb = max(1, self.cfg.bucket_blocks)
-        self.bucket_after: Dict[int, int] = {}
-        bounds = []
-        end = self.train_hi  # frozen tensors (past train_hi) are never reduced
-        j = 0
-        for i in range(L - 1, -1, -1):
-            if ((L - 1 - i) % bb == bb - 1 and i > 0) or (i == 0 and self.cfg.embed_bucket):
-                bounds.append((starts[i], end))
-                self.bucket_after[i] = j
-                end = starts[i]
-                j += 1
-        bounds.append((0, end))
-        self.bucket_after[-1] = j
-        self.buckets = bounds
-        # sub-ranges actually all-reduced per bucket (inactive time_embed rows skipped)
-        self.bucket_ranges = []
-        to, tn = self.offsets["time_embed.weight"]
-        rows = self.cfg.temb_rows
-        skip = None
-        if rows is not None and 0 < rows < self.prog.cfg.total_steps:
-            skip = (to + rows * c.dim, to + tn)
-        for a, b in bounds:
-            if skip is not None and a <= skip[0] and skip[1] <= b:
-                self.bucket_ranges.append([r for r in ((a, skip[0]), (skip[1], b)) if r[1] > r[0]])
-            else:
-                self.bucket_ranges.append([(a, b)])
-        self.temb_bucket = None
-        if (self.cfg.temb_sparse and self.segmented and self.grad_tensors.temb is not None
-                and (rows is None or rows >= self.prog.cfg.total_steps)):
-            for k, (a, b) in enumerate(bounds):
-                if a <= to and to + tn <= b:
-                    self.temb_bucket = k
-                    self.bucket_ranges[k] = [r for a2, b2 in self.bucket_ranges[k]
-                                             for r in ((a2, min(b2, to)), (max(a2, to + tn), b2)) if r[1] > r[0]]
-        # LN index range finalised at each bucket boundary (backward order)
-        self.ln_done_at = {}
-        done = 1
-        for i in range(L - 1, -1, -1):
-            done += 2
-            if i in self.bucket_after:
-                self.ln_done_at[i] = done
-        self.ln_done_at[-1] = len(self.ln_order)
 
     def _refresh_shadow(self):
         self.flat_pb.copy_(self.flat_p.to(torch.bfloat16))
@@ -737,10 +610,10 @@ class TrainEngine:
             d = step_decisions(cfg, sw, self.world, self.segmented, self.is_cuda, B,
                                self.grad_tensors.temb is not None)
             tail = self.lnfold is not None
-            hi = self.ln_done_at[-1]
+            hi = self.bucketing.ln_done_at[-1]
             ln_final = ops.LnFinal(self.ln_ws[:hi], self.ln_ptrs[:hi], 2 * c.dim, self.ln_R, d["overwrite"],
-                                   self._ln_offs()[:hi]) if d["ln_final"] else None
-            flush_at = frozenset(k for k in self.bucket_after if k >= 0) if self.segmented else None
+                                   list(self.layout.ln_offs[:hi])) if d["ln_final"] else None
+            flush_at = frozenset(k for k in self.bucketing.bucket_after if k >= 0) if self.segmented else None
             owners = self._emb_owners(B) if d["embed_fused"] else None
             bwd = BackwardPlan(ln_ws=self.ln_ws, embed_with_block0=d["merge"], ln_final=ln_final, flush_at=flush_at,
                                store=d["overwrite"], owners=owners, tickets=self.wgrad_tickets,
@@ -792,11 +665,11 @@ class TrainEngine:
         if plan.k_acc > 1:  # mean over micro-batches (partials sum to each micro-batch's loss)
             lp = loss_parts.float() * (1.0 / plan.k_acc)
             loss_parts = lp if loss_acc is None else loss_acc + lp
-        ln_lo = 0
+        ln_lo, bk = 0, self.bucketing
         for i in self.prog.backward_iter(self.param_tensors, self.grad_tensors, S, dtok, self.rng, True,
                                          plan=plan.backward):
-            if i in self.bucket_after and (self.segmented or i == -1):
-                hi = self.ln_done_at[i]
+            if i in bk.bucket_after and (self.segmented or i == -1):
+                hi = bk.ln_done_at[i]
                 if plan.ln_final is not None:
                     ln_lo = hi  # already finalized by the embedding backward
                 if hi > ln_lo:
@@ -804,7 +677,7 @@ class TrainEngine:
                                         2 * c.dim, self.ln_R, dsts=self.ln_dsts[ln_lo:hi])
                     ln_lo = hi
                 if last:
-                    yield ("bucket", self.bucket_after[i])
+                    yield ("bucket", bk.bucket_after[i])
         return loss_parts
 
     def _optimizer_tail(self, plan: StepPlan, loss_parts):
@@ -819,7 +692,7 @@ class TrainEngine:
         ema = {} if self.opt_e is None else dict(ema=self.opt_e, ema_decay=cfg.weight_ema,
                                                  ema_warmup=cfg.weight_ema_warmup)
         ops.adamw_step(self.opt_p, self.opt_g, self.opt_m, self.opt_v, self.opt_pb, self.sqnorm,
-                       self.step_ctr, self.hyper, gs, zero_hi=self.acc_hi if plan.overwrite else None,
+                       self.step_ctr, self.hyper, gs, zero_hi=self.layout.acc_hi if plan.overwrite else None,
                        lazy=self.lazy, lazy_decay=self.lazy_decay, **ema)
         if self.wt is not None:  # the input-gradient GEMMs' transposed shadows of the new weights
             self.wt.refresh()
@@ -841,7 +714,7 @@ class TrainEngine:
         here on the current stream."""
         if self.ncomm is None and (not self.dist_on or (self.world <= 1 and not self.cfg.force_segments)):
             return
-        ranges = self.bucket_ranges[k]
+        ranges = self.bucketing.ranges[k]
 
         fake = os.environ.get("DDIM_COLD_FAKE_COMM") == "1"
 
@@ -868,7 +741,7 @@ class TrainEngine:
                     ops.wire_pack(self.flat_g[a:b], w)
                     dist.all_reduce(w, group=self.pg)
                     ops.wire_unpack(w, self.flat_g[a:b])
-            if k == self.temb_bucket:
+            if k == self.bucketing.temb_bucket:
                 self._temb_exchange()
 
         if self.comm is not None:
@@ -961,21 +834,19 @@ class TrainEngine:
         active time_embed rows) on the wire, backward timing scaled from the
         measured ViT-tiny step by this batch's GEMM work."""
         from ..parallel import costmodel as cm
-        c = self.prog.cfg
+        c, lay = self.prog.cfg, self.layout
         wire = 2 if self.cfg.grad_wire == "bf16" else 4
-        hidden = self.offsets["blocks.0.mlp.fc1.bias"][1]
         xb = getattr(self.batch_fn, "x_t", None)
         B = int(xb.shape[0]) if isinstance(xb, torch.Tensor) else 32
-        prof = cm.vit_step_profile(c.depth, c.dim, hidden, B * c.tokens, 0, wire_bytes=wire)
-        head = sum(self.offsets[n][1] for n in ("head.weight", "head.bias") if n in self.offsets)
-        prof.head_bytes = float(head * wire)
-        other = max(0.0, self.reduced_numel() - c.depth * prof.block_bytes / wire - head)
+        prof = cm.vit_step_profile(c.depth, c.dim, c.hidden, B * c.tokens, 0, wire_bytes=wire)
+        prof.head_bytes = float(lay.head_numel * wire)
+        other = max(0, self.reduced_numel() - c.depth * lay.block_numel - lay.head_numel)
         prof.embed_bytes = float(other * wire)
         return prof
 
     def reduced_numel(self) -> int:
         """Elements all-reduced per step (inactive time_embed rows / frozen tensors skipped)."""
-        return sum(b - a for rs in self.bucket_ranges for a, b in rs)
+        return self.bucketing.reduced_numel
 
     def probe_allreduce(self, sizes_mb=(0.25, 1.0, 4.0, 16.0), reps: int = 10):
         """Measure the gradient all-reduce on THIS job's ranks (the engine's own comm
@@ -1233,7 +1104,7 @@ class TrainEngine:
         for kind, k in self._step_iter():
             if kind == "bucket":
                 self._allreduce(k)
-                if k == len(self.buckets) - 1:
+                if k == len(self.bucketing.bounds) - 1:
                     self._join_comm()
 
     def _drop_capture(self, rewarm: bool):
@@ -1303,7 +1174,7 @@ class TrainEngine:
         for.  Inline layout (no comm stream): the boundaries leave nothing in the graph."""
         from ..parallel.comm import FlagSignal
         pool = torch.cuda.graph_pool_handle()
-        nb = len(self.buckets)
+        nb = len(self.bucketing.bounds)
         sig = FlagSignal(nb, self.device) if self.comm is not None else None
         gen = self._step_iter()
         g1, g2 = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
@@ -1338,7 +1209,7 @@ class TrainEngine:
         pool = torch.cuda.graph_pool_handle()
         gen = self._step_iter()
         graphs = []
-        for _ in range(len(self.buckets) + 1):
+        for _ in range(len(self.bucketing.bounds) + 1):
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, pool=pool, capture_error_mode=CAPTURE_MODE):
                 next(gen)
@@ -1346,7 +1217,7 @@ class TrainEngine:
         return graphs
 
     def _replay(self):
-        gs, nb = self._graphs, len(self.buckets)
+        gs, nb = self._graphs, len(self.bucketing.bounds)
         if self._mode == SINGLE:
             gs[0].replay()
         elif self._mode == EVENT_SPLIT:
@@ -1483,12 +1354,13 @@ class TrainEngine:
 
     def _arena_state_dict(self, flat: torch.Tensor) -> Dict[str, torch.Tensor]:
         """The model's ``state_dict`` (keys, shapes, order) read from an arena."""
-        shapes = {n: p.shape for n, p in self.model.named_parameters()}
+        lay = self.layout
+        shapes = dict(zip(lay.names, lay.shapes))
         out = {}
         for n in self.model.state_dict().keys():
-            if n not in self.offsets:
+            if n not in lay.offsets:
                 raise KeyError(f"{n}: not in the parameter arena (a buffer?)")
-            o, k = self.offsets[n]
+            o, k = lay.offsets[n]
             out[n] = flat[o:o + k].view(shapes[n]).clone()
         return out
 
@@ -1501,10 +1373,11 @@ class TrainEngine:
         """Restore the EMA arena from a ``state_dict`` of the model's keys (strict)."""
         self._need_ema("load_ema_state_dict()")
         self._no_ema_scope("load_ema_state_dict")
-        if set(sd) != set(self.offsets):
+        have = set(self.layout.names)
+        if set(sd) != have:
             raise KeyError(f"EMA state dict keys differ from the model's: missing "
-                           f"{sorted(set(self.offsets) - set(sd))}, unexpected {sorted(set(sd) - set(self.offsets))}")
-        for n, (o, k) in self.offsets.items():
+                           f"{sorted(have - set(sd))}, unexpected {sorted(set(sd) - have)}")
+        for n, (o, k) in self.layout.offsets.items():
             self.flat_e[o:o + k].copy_(sd[n].reshape(-1).to(self.device, torch.float32))
 
     # ------------------------------------------------------------------ state
@@ -1531,14 +1404,15 @@ class TrainEngine:
         params = self._param_list()
         opt = torch.optim.AdamW(params, lr=self._lr_at(sched_step), betas=self.cfg.betas, eps=self.cfg.eps,
                                 weight_decay=self.cfg.weight_decay)
+        lay = self.layout
         if adam_step > 0:
-            for n, p in zip(self.names, params):
-                if n in self.frozen:  # torch.optim keeps no state for a parameter without .grad
+            for n, shape, p in zip(lay.names, lay.shapes, params):
+                if n in lay.frozen:  # torch.optim keeps no state for a parameter without .grad
                     continue
-                o, k = self.offsets[n]
+                o, k = lay.offsets[n]
                 opt.state[p] = {"step": torch.tensor(float(adam_step)),
-                                "exp_avg": flat_m[o:o + k].view(p.shape).clone(),
-                                "exp_avg_sq": flat_v[o:o + k].view(p.shape).clone()}
+                                "exp_avg": flat_m[o:o + k].view(shape).clone(),
+                                "exp_avg_sq": flat_v[o:o + k].view(shape).clone()}
         sd = opt.state_dict()
         sd["param_groups"][0]["initial_lr"] = self.cfg.lr
         return sd
@@ -1580,13 +1454,13 @@ class TrainEngine:
 
     def load_optimizer_state_dict(self, sd: dict):
         st = sd.get("state", {})
-        params = self._param_list()
+        lay = self.layout
         step = 0
-        for i, (n, p) in enumerate(zip(self.names, params)):
+        for i, n in enumerate(lay.names):
             s = st.get(i)
-            if s is None or n in self.frozen:
+            if s is None or n in lay.frozen:
                 continue
-            o, k = self.offsets[n]
+            o, k = lay.offsets[n]
             self.flat_m[o:o + k].copy_(s["exp_avg"].reshape(-1).to(self.device))
             self.flat_v[o:o + k].copy_(s["exp_avg_sq"].reshape(-1).to(self.device))
             step = int(float(s["step"]))

@@ -91,7 +91,7 @@ def test_every_invalidation_drops_the_whole_capture(case, monkeypatch):
     def captured(mode_, order_):
         torch.cuda.synchronize()
         assert eng._mode == mode_ and eng.handoff_order == order_
-        assert len(eng._graphs) == {SINGLE: 1, EVENT_SPLIT: 2, SEGMENTS: len(eng.buckets) + 1}[mode_]
+        assert len(eng._graphs) == {SINGLE: 1, EVENT_SPLIT: 2, SEGMENTS: len(eng.bucketing.bounds) + 1}[mode_]
         assert (eng._signal is not None) == (order_ in ("pre-issued", "post-replay"))
         assert not eng._graph_comm_failed
         assert (eng._multi is not None) == (mode_ == SINGLE and eng.cfg.graph_steps > 1)

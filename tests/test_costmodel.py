@@ -79,7 +79,7 @@ def test_engine_layout_names_and_model_candidates():
     for bb in (1, 2, 3, 4, 7):
         for eb in (True, False):
             eng.set_comm_layout(bb, eb)
-            got = [4 * sum(b - a for a, b in rs) for rs in eng.bucket_ranges]
+            got = [4 * sum(b - a for a, b in rs) for rs in eng.bucketing.ranges]
             want = [nb for _, nb in cm.bucket_plan(prof, bb, eb)]
             assert got == pytest.approx(want), (bb, eb)
     eng.world = 2

@@ -67,14 +67,14 @@ def _world_worker(rank, world, port, out_path):
         for name, wire, gauss, layout in VARIANTS:
             eng = _engine(wire, gauss, seed=rank)  # different init per rank: rank 0's is broadcast
             eng.apply_layout(layout)
-            assert (eng.temb_bucket is not None) == (gauss and layout != "inline-1") or gauss
+            assert (eng.bucketing.temb_bucket is not None) == (gauss and layout != "inline-1") or gauss
             x, y, t = _batch(gauss)
             sl = slice(rank * b, (rank + 1) * b)
             eng.step(x[sl], y[sl], t[sl])
             m = eng.flat_m.clone()
             ms = [torch.zeros_like(m) for _ in range(world)]
             dist.all_gather(ms, m)
-            res[name] = (m, all(torch.equal(ms[0], q) for q in ms), len(eng.buckets))
+            res[name] = (m, all(torch.equal(ms[0], q) for q in ms), len(eng.bucketing.bounds))
         if rank == 0:
             torch.save(res, out_path)
     finally:
@@ -92,7 +92,7 @@ def test_data_parallel_world_matches_single_process(world):
     for gauss in (False, True):
         eng = _engine("fp32", gauss, seed=0)
         eng.step(*_batch(gauss))
-        refs[gauss] = (eng.flat_m.clone(), eng.offsets["time_embed.weight"])
+        refs[gauss] = (eng.flat_m.clone(), eng.layout.offsets["time_embed.weight"])
     for name, wire, gauss, layout in VARIANTS:
         m, same, nb = res[name]
         assert same, f"{name}: replicas differ"

@@ -108,9 +108,9 @@ def test_engine_frozen_sinusoidal_table_matches_torch_adamw():
     assert torch.equal(model.time_embed.weight.detach(), table0)
     cfg = EngineConfig(lr=1e-3, t_max=20, max_grad_norm=0.05, seed=11)  # decay would move every element
     eng = TrainEngine(model, cfg, device="cpu")
-    assert "time_embed.weight" in eng.frozen and eng.offsets["time_embed.weight"][0] >= eng.train_hi
+    assert "time_embed.weight" in eng.layout.frozen and eng.layout.offsets["time_embed.weight"][0] >= eng.layout.train_hi
     assert model.time_embed.weight.grad is None
-    assert all(b <= eng.train_hi for _, b in eng.buckets)
+    assert all(b <= eng.layout.train_hi for _, b in eng.bucketing.bounds)
     opt = torch.optim.AdamW(ref_model.parameters(), lr=1e-3, betas=cfg.betas, eps=cfg.eps, weight_decay=0.05)
     sched = torch.optim.lr_scheduler.CosineAnnealingLR(opt, 20)
     for step in range(3):
@@ -141,15 +141,39 @@ def test_engine_params_are_arena_views():
     model = _model()
     eng = TrainEngine(model, EngineConfig(), device="cpu")
     for n, p in model.named_parameters():
-        o, k = eng.offsets[n]
+        o, k = eng.layout.offsets[n]
         assert p.data.data_ptr() == eng.flat_p[o:].data_ptr()
         assert p.grad.data_ptr() == eng.flat_g[o:].data_ptr()
         is_ln_bias = n.endswith(".bias") and p.dim() == 1 and "norm" in n
         assert o % 64 == 0 or (is_ln_bias and o % 4 == 0), n
     # buckets tile the arena exactly
-    cover = sorted(eng.buckets)
-    assert cover[0][0] == 0 and cover[-1][1] == eng.numel
+    cover = sorted(eng.bucketing.bounds)
+    assert cover[0][0] == 0 and cover[-1][1] == eng.layout.numel
     assert all(a[1] == b[0] for a, b in zip(cover, cover[1:]))
+
+
+def test_engine_follows_its_layout():
+    """The engine's views are the ranges ``eng.layout`` names, and ``eng.bucketing`` is the
+    ``bucket_layout`` of the current configuration, also after a layout switch."""
+    from ddim_cold_amd.train.layout import bucket_layout
+    model = _model()
+    eng = TrainEngine(model, EngineConfig(temb_rows=7, force_segments=True), device="cpu")
+    assert eng.layout.names == tuple(n for n, _ in model.named_parameters())
+    for n, p in model.named_parameters():
+        o, k = eng.layout.offsets[n]
+        for view, flat in ((p.data, eng.flat_p), (p.grad, eng.flat_g)):
+            assert view.data_ptr() == flat[o:].data_ptr() and view.numel() == k and view.is_contiguous(), n
+            assert view.untyped_storage().data_ptr() == flat.untyped_storage().data_ptr(), n
+    D = model.embed_dim
+    assert len(eng.ln_dsts) == len(eng.layout.ln_offs) == 2 * model.depth + 1
+    for dst, o in zip(eng.ln_dsts, eng.layout.ln_offs):
+        assert dst.data_ptr() == eng.flat_g[o:].data_ptr() and dst.numel() == 2 * D
+    assert eng.lazy == eng.layout.lazy and eng.lazy is not None
+    assert eng.bucketing == bucket_layout(eng.layout, 2, True, True)
+    eng.set_comm_layout(3, False)
+    assert (eng.cfg.bucket_blocks, eng.cfg.embed_bucket) == (3, False)
+    assert eng.bucketing == bucket_layout(eng.layout, 3, False, True)
+    assert len(eng.bucketing.bounds) == 1 and eng.reduced_numel() == eng.bucketing.reduced_numel
 
 
 def test_nonfinite_grad_skips_update():
@@ -172,13 +196,13 @@ def _ddp_worker(rank, world, port, out_path, wire="fp32", gauss=False):
                                               temb_rows=None if gauss else 7, grad_wire=wire), device="cpu")
         # inactive time_embed rows skipped (cold) or the whole table exchanged as
         # all-gathered rows (Gaussian); the embeddings have their own last bucket
-        reduced = sum(b - a for rs in eng.bucket_ranges for a, b in rs)
-        assert reduced == eng.numel - (2000 - (0 if gauss else 7)) * model.embed_dim
-        assert (eng.temb_bucket is not None) == gauss
-        assert eng.bucket_ranges[-1][-1][1] <= eng.offsets["blocks.0.attn.qkv.weight"][0]
+        reduced = sum(b - a for rs in eng.bucketing.ranges for a, b in rs)
+        assert reduced == eng.layout.numel - (2000 - (0 if gauss else 7)) * model.embed_dim
+        assert (eng.bucketing.temb_bucket is not None) == gauss
+        assert eng.bucketing.ranges[-1][-1][1] <= eng.layout.offsets["blocks.0.attn.qkv.weight"][0]
         # every LayerNorm sits in the last (embedding) bucket: finalised once, after block 0
-        last = eng.buckets[-1]
-        assert all(last[0] <= eng.offsets[n][0] < last[1] for n in eng.names if ".norm" in n or n.startswith("norm"))
+        last = eng.bucketing.bounds[-1]
+        assert all(last[0] <= eng.layout.offsets[n][0] < last[1] for n in eng.layout.names if ".norm" in n or n.startswith("norm"))
         x, y, t = _batch(4, seed=5)
         t = t % 6 + 1 if not gauss else t[[0, 0, 1, 0]]  # cold timesteps / repeats across and within ranks
         b = 4 // world
@@ -211,7 +235,7 @@ def test_data_parallel_gloo_matches_single_process(wire, tol, gauss):
     # exp_avg after one step = (1-b1) * mean-gradient
     err = (r["m"] - m1).abs().max().item() / m1.abs().max().item()
     assert err < tol, err
-    o, k = eng.offsets["time_embed.weight"]
+    o, k = eng.layout.offsets["time_embed.weight"]
     te, te1 = r["m"][o:o + k], m1[o:o + k]
     assert te1.abs().max() > 0 and (te - te1).abs().max().item() < tol * te1.abs().max().item()
 
@@ -336,11 +360,11 @@ def _layout_worker(rank, world, port, out_path):
             name = L[0]
             eng.apply_layout(L)
             assert eng.comm_choice == name and eng.cfg.comm_events == (not name.startswith("graph-"))
-            cover = sorted(eng.buckets)  # buckets tile the arena for every layout
-            assert cover[0][0] == 0 and cover[-1][1] == eng.numel
+            cover = sorted(eng.bucketing.bounds)  # buckets tile the arena for every layout
+            assert cover[0][0] == 0 and cover[-1][1] == eng.layout.numel
             assert all(a[1] == c[0] for a, c in zip(cover, cover[1:]))
             if name.endswith("inline-1"):
-                assert len(eng.buckets) == 1 and eng.comm is None
+                assert len(eng.bucketing.bounds) == 1 and eng.comm is None
             eng.step(xb, yb, tb)
             eng.step(xb, yb, tb)
             res[name] = (eng.flat_p.clone(), eng.flat_m.clone(), eng.loss_ema.clone())
@@ -381,7 +405,7 @@ def test_lazy_time_embed_decay_matches_torch_adamw():
     eng = TrainEngine(model, cfg, device="cpu")
     assert eng.lazy is not None
     lo, hi = eng.lazy
-    o, k = eng.offsets["time_embed.weight"]
+    o, k = eng.layout.offsets["time_embed.weight"]
     assert lo == o + 7 * model.embed_dim and hi == o + k
     opt = torch.optim.AdamW(ref_model.parameters(), lr=1e-3, betas=cfg.betas, eps=cfg.eps, weight_decay=0.05)
     sched = torch.optim.lr_scheduler.CosineAnnealingLR(opt, 5)

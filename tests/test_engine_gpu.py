@@ -169,8 +169,8 @@ def test_ln_replica_finalize_fused_matches_separate(monkeypatch):
         eng.set_batch_fn(ColdBatcher(synthetic_pool(64, seed=1, device="cuda"), 8, eng.rng))
         eng.train_step()
         torch.cuda.synchronize()
-        ln = torch.cat([eng.flat_p[eng.offsets[n + ".weight"][0]:eng.offsets[n + ".weight"][0] + 2 * model.embed_dim]
-                        for n in eng.ln_order])
+        ln = torch.cat([eng.flat_p[eng.layout.offsets[n + ".weight"][0]:eng.layout.offsets[n + ".weight"][0] + 2 * model.embed_dim]
+                        for n in eng.layout.ln_order])
         # the step must have touched every LayerNorm parameter
         return ln.clone(), eng.flat_m.clone()
     lf, mf = run("1")
@@ -198,10 +198,10 @@ def test_gradient_overwrite_matches_accumulate(monkeypatch):
         return eng.flat_p.clone(), losses, eng
     po, lo, eng = run("1")
     pa, la, eng_a = run("0")
-    assert eng.acc_hi < eng.offsets["blocks.0.attn.qkv.weight"][0]
+    assert eng.layout.acc_hi < eng.layout.offsets["blocks.0.attn.qkv.weight"][0]
     # overwrite mode leaves the last step's gradients above acc_hi in place; accumulate zeroes all
-    assert eng.flat_g[eng.acc_hi:].abs().max() > 0 and eng_a.flat_g.abs().max() == 0
-    assert eng.flat_g[:eng.acc_hi].abs().max() == 0
+    assert eng.flat_g[eng.layout.acc_hi:].abs().max() > 0 and eng_a.flat_g.abs().max() == 0
+    assert eng.flat_g[:eng.layout.acc_hi].abs().max() == 0
     assert all(abs(a - b) <= 1e-4 * abs(b) for a, b in zip(lo, la)), (lo, la)
     assert (po - pa).abs().max().item() <= 2 * 1e-3 * 5
 

@@ -52,7 +52,7 @@ def test_two_engines_cross_queue_handoff(layout, K, monkeypatch):
     monkeypatch.setenv("DDIM_COLD_HANDOFF_TIMEOUT_US", str(TIMEOUT_US))
     x, y, t = _batch(2 * B)
     engs = [_engine(True, K), _engine(True, K)]
-    pair = LoopbackPair("cuda", engs[0].numel, timeout_us=TIMEOUT_US)
+    pair = LoopbackPair("cuda", engs[0].layout.numel, timeout_us=TIMEOUT_US)
     streams = [torch.cuda.Stream(), torch.cuda.Stream()]
     for e, eng in enumerate(engs):
         eng.attach_comm(pair.endpoint(e), 2)
@@ -112,6 +112,6 @@ def test_attach_comm_rejects_sparse_temb_engine_without_all_gather():
     torch.manual_seed(100)
     model = build_model("vit_tiny").cuda().train()
     eng = TrainEngine(model, EngineConfig(lr=LR, t_max=100, seed=5, temb_rows=None, force_segments=True))
-    pair = LoopbackPair("cuda", eng.numel)
+    pair = LoopbackPair("cuda", eng.layout.numel)
     with pytest.raises(ValueError, match="all_gather_"):
         eng.attach_comm(pair.endpoint(0), 2)

@@ -125,7 +125,7 @@ def test_engine_ema_follows_hand_loop_and_leaves_training_alone():
     assert _engine(0.0).lazy is not None  # the same rows ARE lazy without the EMA
     e = eng.flat_p.clone()
     assert torch.equal(eng.flat_e, e) and eng.flat_e.data_ptr() != eng.flat_p.data_ptr()
-    th = eng.train_hi
+    th = eng.layout.train_hi
     for s in range(6):
         eng.step(*_batch(4, s))
         off.step(*_batch(4, s))
@@ -185,7 +185,7 @@ def test_ema_scope():
     eng.detach()
     assert model._engine is None and eng._ema_tmp is None
     assert all(p.data_ptr() != eng.flat_p[o:].data_ptr() for (n, p), (o, _) in
-               zip(model.named_parameters(), (eng.offsets[n] for n, _ in model.named_parameters())))
+               zip(model.named_parameters(), (eng.layout.offsets[n] for n, _ in model.named_parameters())))
 
 
 def test_snapshot_and_autotune_state_hold_the_ema():

@@ -26,7 +26,7 @@ def run(dist_mode, comm="torch", wire="fp32", gauss=False, tune=False, layout=No
     pool = synthetic_pool(64, seed=3, device="cuda")
     # Gaussian diffusion (t over the whole table): sparse time_embed row exchange
     eng.set_batch_fn(GaussianBatcher(pool, 16, eng.rng, 2000) if gauss else ColdBatcher(pool, 16, eng.rng))
-    assert (eng.temb_bucket is not None) == (gauss and dist_mode is not None)
+    assert (eng.bucketing.temb_bucket is not None) == (gauss and dist_mode is not None)
     if layout is not None:
         eng.apply_layout(layout)
     if tune:  # measures every layout, then restores the training state
