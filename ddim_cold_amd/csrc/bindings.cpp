@@ -1157,6 +1157,39 @@ void cold_step_rows_(Tensor x, Tensor x0, Tensor t, int64_t batch, int64_t C, in
   cold_step_impl(x, x0, t, batch, C, H, W, patch, algorithm, patches_out, true);
 }
 
+// Inpainting mask step on the sampler's patch rows (csrc/diffusion.hip repaint_rows_kernel),
+// in place on x; every check before the launch.
+void repaint_rows_(Tensor x, Tensor known, Tensor mask, Tensor coef, Tensor rng, int64_t site_paste,
+                   int64_t site_jump, c10::optional<Tensor> patches_out) {
+  CHECK_IN(x, F32); CHECK_IN(known, F32); CHECK_IN(mask, at::kByte); CHECK_IN(coef, F32); check_rng(rng);
+  const c10::DeviceGuard guard(x.device());
+  TORCH_CHECK(known.device() == x.device() && mask.device() == x.device() && coef.device() == x.device() &&
+                  rng.device() == x.device(), "repaint_rows_: x, known, mask, coef and rng on one device");
+  TORCH_CHECK(known.sizes() == x.sizes() && mask.sizes() == x.sizes(), "repaint_rows_: x, known and mask of one shape");
+  const int64_t n = x.numel();
+  TORCH_CHECK(n % 4 == 0, "repaint_rows_: the element count must be a multiple of 4");
+  TORCH_CHECK(n < ((int64_t)1 << 31), "repaint_rows_: 32-bit indexing needs fewer than 2^31 elements");
+  TORCH_CHECK(coef.numel() == 4, "repaint_rows_: coef must hold {ka, kb, ra, rb}");
+  TORCH_CHECK(rng.numel() == 2, "repaint_rows_: rng must be int64[2] {seed, 0}");
+  TORCH_CHECK(site_paste >= 0 && site_jump >= 0 && site_paste <= INT32_MAX && site_jump <= INT32_MAX,
+              "repaint_rows_: noise sites must be non-negative ints");
+  const char *xp = (const char*)x.data_ptr(), *kp = (const char*)known.data_ptr();
+  TORCH_CHECK(xp + n * 4 <= kp || kp + n * 4 <= xp, "repaint_rows_: x and known must not alias");
+  TORCH_CHECK((uintptr_t)xp % 16 == 0 && (uintptr_t)kp % 16 == 0, "repaint_rows_: x and known must be 16-byte aligned");
+  TORCH_CHECK((uintptr_t)mask.data_ptr() % 4 == 0, "repaint_rows_: mask must be 4-byte aligned");
+  void* po = nullptr;
+  if (patches_out.has_value() && patches_out->defined()) {
+    CHECK_IN((*patches_out), BF16);
+    TORCH_CHECK(patches_out->device() == x.device() && patches_out->sizes() == x.sizes(),
+                "repaint_rows_: patches_out must be on x's device and of its shape");
+    po = patches_out->data_ptr();
+    TORCH_CHECK((uintptr_t)po % 8 == 0, "repaint_rows_: patches_out must be 8-byte aligned");
+  }
+  if (n == 0) return;
+  repaint_rows_launch(x.data_ptr<float>(), known.data_ptr<float>(), mask.data_ptr<uint8_t>(), coef.data_ptr<float>(),
+                      rng.data_ptr<int64_t>(), (int)site_paste, (int)site_jump, po, n, cur_stream());
+}
+
 void randn_(Tensor out, Tensor rng, int64_t site) {
   CHECK_IN(out, F32); check_rng(rng);
   const c10::DeviceGuard guard(out.device());
@@ -1349,6 +1382,8 @@ TORCH_LIBRARY(ddim_cold, m) {
   m.def("cold_step_(Tensor(a!) x, Tensor x0, Tensor t, int algorithm, int patch, Tensor(b!)? patches_out) -> ()");
   m.def("cold_step_rows_(Tensor(a!) x, Tensor x0, Tensor t, int batch, int C, int H, int W, int patch, "
         "int algorithm, Tensor(b!)? patches_out) -> ()");
+  m.def("repaint_rows_(Tensor(a!) x, Tensor known, Tensor mask, Tensor coef, Tensor rng, int site_paste, "
+        "int site_jump, Tensor(b!)? patches_out) -> ()");
   m.def("randn_(Tensor(a!) out, Tensor rng, int site) -> ()");
   m.def("q_sample(Tensor x0, Tensor t, Tensor eps, int total_steps) -> Tensor");
   m.def("pixelate_pair(Tensor img, Tensor? idx, Tensor t, int B) -> (Tensor, Tensor)");
@@ -1398,6 +1433,7 @@ TORCH_LIBRARY_IMPL(ddim_cold, CUDA, m) {
   m.impl("ddim_step_", &ddim_step_);
   m.impl("cold_step_", &cold_step_);
   m.impl("cold_step_rows_", &cold_step_rows_);
+  m.impl("repaint_rows_", &repaint_rows_);
   m.impl("randn_", &randn_);
   m.impl("q_sample", &q_sample);
   m.impl("pixelate_pair", &pixelate_pair);

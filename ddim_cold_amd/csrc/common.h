@@ -61,6 +61,13 @@ __device__ __forceinline__ bf16x8 frag_t(const char* lds, int c0, int s, int lan
   return v;
 }
 
+// v as it stands in its register: the product or sum that made it is rounded on its own, the
+// compiler cannot fuse it into a multiply-add with an operation on either side of it
+__device__ __forceinline__ float rounded(float v) {
+  asm volatile("" : "+v"(v));
+  return v;
+}
+
 // ----------------------------------------------------------------------------- write-through stores
 // Output stores that go through L2 to memory as they are issued (sc1), so a kernel leaves
 // no dirty lines for the write-back at its end.  Same bytes, same addresses, same lanes as

@@ -11,6 +11,9 @@
 //  * pixelate_pair / cold_batch: the cold degradation of diffusion_loader.py:79-97
 //    (NEAREST down to floor(W/2^t), NEAREST back up) for (t, t-1) in one pass;
 //    cold_batch also draws the batch (pool index, t in 1..max_t) on device.
+//  * cold_step / repaint_rows: the per-step launches of the cold x0 sampler and of inpainting
+//    (paste the kept region at the step's noise level, jump back for a resample), in place
+//    on the sampler state.
 #include "common.h"
 #include "kernels.h"
 
@@ -212,6 +215,56 @@ __global__ __launch_bounds__(256) void cold_step_kernel(float* __restrict__ x, c
   }
 }
 
+// Mask step of inpainting (RePaint, Lugmayr et al. 2022), in place on the sampler's fp32
+// patch-row state x, after the forward whose head epilogue stepped it.  Per element e
+//   y   = mask[e] ? fma(kb, z1[e], rounded(ka known[e])) : x[e]      (paste: known noised to the step's level)
+//   out = (ra == 1 && rb == 0) ? y : fma(rb, z2[e], rounded(ra y))   (jump: diffuse forward again)
+// coef = {ka, kb, ra, rb} from device memory (a captured loop has no host scalars); z1 / z2 =
+// element e of randn_kernel's draw over x at (rng, site_paste) / (rng, site_jump), by gauss_pair.
+// Each thread owns 4 consecutive elements: one 4-byte mask load, 16-byte loads of x / known,
+// a 16-byte store of x and an 8-byte store of its bf16 rows (pout, optional).  A paste-only
+// call (wave-uniform on the loaded coefficients) stores nothing for a 4-vector whose mask bytes
+// are all zero, draws z1 only for a pair with a mask byte set and never z2; a jump writes
+// every element.  n4 = elements / 4 (elements < 2^31).
+__global__ __launch_bounds__(256) void repaint_rows_kernel(float* __restrict__ x, const float* __restrict__ known,
+                                                           const uint8_t* __restrict__ mask,
+                                                           const float* __restrict__ coef,
+                                                           const int64_t* __restrict__ rng, int site_paste,
+                                                           int site_jump, bf16* __restrict__ pout, int n4) {
+  const float ka = coef[0], kb = coef[1], ra = coef[2], rb = coef[3];
+  const bool paste_only = ra == 1.f && rb == 0.f;
+  const uint32_t salt_p = site_salt(rng, site_paste), salt_j = site_salt(rng, site_jump);
+  for (int q = blockIdx.x * 256 + threadIdx.x; q < n4; q += gridDim.x * 256) {
+    const int e = 4 * q;
+    const uint32_t m = *reinterpret_cast<const uint32_t*>(mask + e);
+    if (paste_only && m == 0u) continue;
+    f32x4 v = *reinterpret_cast<const f32x4*>(x + e);
+    if (m != 0u) {
+      const f32x4 kn = *reinterpret_cast<const f32x4*>(known + e);
+      float2 z01 = make_float2(0.f, 0.f), z23 = z01;
+      if (m & 0x0000FFFFu) z01 = gauss_pair(salt_p, (uint32_t)e);
+      if (m & 0xFFFF0000u) z23 = gauss_pair(salt_p, (uint32_t)e + 2u);
+      const float z[4] = {z01.x, z01.y, z23.x, z23.y};
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if ((m >> (8 * j)) & 0xFFu) v[j] = __builtin_fmaf(kb, z[j], rounded(ka * kn[j]));
+    }
+    if (!paste_only) {
+      const float2 z01 = gauss_pair(salt_j, (uint32_t)e), z23 = gauss_pair(salt_j, (uint32_t)e + 2u);
+      v[0] = __builtin_fmaf(rb, z01.x, rounded(ra * v[0]));
+      v[1] = __builtin_fmaf(rb, z01.y, rounded(ra * v[1]));
+      v[2] = __builtin_fmaf(rb, z23.x, rounded(ra * v[2]));
+      v[3] = __builtin_fmaf(rb, z23.y, rounded(ra * v[3]));
+    }
+    *reinterpret_cast<f32x4*>(x + e) = v;
+    if (pout != nullptr) {
+      bf16x4 h;
+      h[0] = f2bf(v[0]); h[1] = f2bf(v[1]); h[2] = f2bf(v[2]); h[3] = f2bf(v[3]);
+      *reinterpret_cast<bf16x4*>(pout + e) = h;
+    }
+  }
+}
+
 static int g_grid(int64_t n) {
   int64_t g = (n + 255) / 256;
   if (g > 4096) g = 4096;
@@ -237,6 +290,12 @@ void cold_step_launch(float* x, const float* x0, const int64_t* t, void* patches
   else
     hipLaunchKernelGGL(cold_step_kernel<false>, grid, dim3(256), 0, stream, x, x0, t, po, B, C, H, W, patch,
                        algorithm);
+}
+
+void repaint_rows_launch(float* x, const float* known, const uint8_t* mask, const float* coef, const int64_t* rng,
+                         int site_paste, int site_jump, void* patches_out, int64_t n, hipStream_t stream) {
+  hipLaunchKernelGGL(repaint_rows_kernel, dim3(g_grid(n / 4)), dim3(256), 0, stream, x, known, mask, coef, rng,
+                     site_paste, site_jump, reinterpret_cast<bf16*>(patches_out), (int)(n / 4));
 }
 
 void randn_launch(float* out, int64_t n, const int64_t* rng, int site, hipStream_t stream) {

@@ -515,13 +515,6 @@ __device__ __forceinline__ float2 stat4(const f32x4& v) {
                      __builtin_fmaf(v[0], v[0], v[1] * v[1]) + __builtin_fmaf(v[2], v[2], v[3] * v[3]));
 }
 
-// v as it stands in its register: the product or sum that made it is rounded on its own, the
-// compiler cannot fuse it into a multiply-add with an operation on either side of it
-__device__ __forceinline__ float rounded(float v) {
-  asm volatile("" : "+v"(v));
-  return v;
-}
-
 __device__ __forceinline__ void st2f(float* p, float2 v) { *reinterpret_cast<float2*>(p) = v; }
 __device__ __forceinline__ float2 ld2f(const float* p) { return *reinterpret_cast<const float2*>(p); }
 __device__ __forceinline__ f32x4 ld4bf(const bf16* p) {

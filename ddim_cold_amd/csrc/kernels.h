@@ -286,6 +286,12 @@ void pixelate_pair_launch(const float* img, const int64_t* idx, const int64_t* t
 // patches_out (optional, bf16) conv-im2col patch rows (patch 0: none).  B*C*H*W < 2^31.
 void cold_step_launch(float* x, const float* x0, const int64_t* t, void* patches_out, int B, int C, int H, int W,
                       int patch, int algorithm, bool rows, hipStream_t stream);
+// Inpainting mask step (RePaint) in place on the fp32 patch rows x: where mask is non-zero
+// x <- ka known + kb z1, then (unless {ra, rb} = {1, 0}) x <- ra x + rb z2 everywhere; coef =
+// device {ka, kb, ra, rb}, z1 / z2 = randn_launch's values at site_paste / site_jump;
+// patches_out (optional): bf16 of what was written.  n = elements, n % 4 == 0, n < 2^31.
+void repaint_rows_launch(float* x, const float* known, const uint8_t* mask, const float* coef, const int64_t* rng,
+                         int site_paste, int site_jump, void* patches_out, int64_t n, hipStream_t stream);
 void randn_launch(float* out, int64_t n, const int64_t* rng, int site, hipStream_t stream);
 void q_sample_launch(const float* x0, const int64_t* t, const float* eps, float* out, int B, int64_t per,
                      int total_steps, hipStream_t stream);

@@ -1,4 +1,4 @@
-"""Samplers: DDIM k-step (+ trajectory), cold de-pixelation, draft->drawing img2img.
+"""Samplers: DDIM k-step (+ trajectory), cold de-pixelation, draft->drawing img2img, inpainting.
 
 Reference behaviour: ``ViT.py:220-256`` (DDIM sampler / sequence),
 ``ViT_draft2drawing.py:259-309`` (cold sampler / sequence),
@@ -20,7 +20,8 @@ Every step is ONE forward whose head-GEMM epilogue applies the step (DDIM
 update, cold clamp, or img2img's DDIM update with per-sample coefficients) and
 hands the next step its bf16 patch rows; the cold sampler of an x0-predicting model
 (``ColdSampler(predict="x0")``) instead follows each forward with one
-:func:`ops.cold_step_` launch.  (Splitting a batch into concurrent
+:func:`ops.cold_step_` launch, and inpainting (:func:`inpaint`) each forward with one
+:func:`ops.repaint_rows_` launch that pastes the kept region back.  (Splitting a batch into concurrent
 chains on separate streams measured slower on MI355X -- ViT-tiny N=64 k=20:
 46.9 / 56.2 / 76.2 ms for 1 / 2 / 4 chains -- and was removed.)
 """
@@ -34,7 +35,7 @@ import torch
 from .. import ops
 from ..models.program import HeadStep, fold_width_ok, model_tensors
 from .schedule import (ETA_IDENT_ROW, cold_steps, ddim_coefficients, ddim_coefficients_eta, ddim_table,
-                       ddim_table_eta, eta_row, img2img_alpha)
+                       ddim_table_eta, eta_row, img2img_alpha, repaint_table)
 
 
 def _use_fused(model, device) -> bool:
@@ -169,6 +170,10 @@ class _Rows:
         N, C, H, W = self.shape
         ops.cold_step_rows_(self.x, self.x0, t, N, C, H, W, self.p, algorithm, patches_out=self.pin)
 
+    def repaint(self, known, mask, coef, rng, site_paste: int, site_jump: int):
+        """Inpainting mask step on ``x`` (``known`` / ``mask`` as patch rows), its bf16 rows into ``pin``."""
+        ops.repaint_rows_(self.x, known, mask, coef, rng, site_paste, site_jump, patches_out=self.pin)
+
     def image(self, xr):
         return ops.rows_to_image(xr, *self.shape, self.p)
 
@@ -189,6 +194,7 @@ class _Image:
 
     def __init__(self, model, N: int, device, den, x, x0=None, chain: bool = True):
         self.den, self.x = den, x
+        self.p = model.patch_size
         self.x0 = torch.zeros_like(x) if x0 is None else x0
         self.pbuf = _patch_rows(model, N, device, den) if chain else None
         self.ident = torch.tensor([0.0, 1.0, 0.0, 1.0], device=device)
@@ -210,6 +216,13 @@ class _Image:
     def cold_step(self, t, algorithm: int):
         ops.cold_step_(self.x, self.x0, t, algorithm, patches_out=self.pbuf)
 
+    def repaint(self, known, mask, coef, rng, site_paste: int, site_jump: int):
+        """Inpainting mask step (``known`` / ``mask`` as patch rows): ``x`` goes through the row
+        layout around the op, as :meth:`_StepNoise.add_`'s noise does (a loop without a chain)."""
+        xr = ops.image_to_rows(self.x, self.p).contiguous()
+        ops.repaint_rows_(xr, known, mask, coef, rng, site_paste, site_jump)
+        self.x.copy_(ops.rows_to_image(xr, *self.x.shape, self.p))
+
     def image(self, xr):
         return xr
 
@@ -217,15 +230,16 @@ class _Image:
         pass
 
 
-def _loop_state(model, N: int, device, den, x, x0=None, eta: bool = False):
+def _loop_state(model, N: int, device, den, x, x0=None, eta: bool = False, chain: bool = True):
     """The state a loop steps: patch rows on the GPU's fused path, else the image layout on
     the loop's buffers ``x`` / ``x0``.  ``eta``: a stochastic loop, whose step is a head mode
     of the patch-row epilogue of the LayerNorm-folded program only; on the image layout its
-    noise changes ``x`` after the head wrote the bf16 rows, so there is no patch-row chain."""
+    noise changes ``x`` after the head wrote the bf16 rows, so there is no patch-row chain
+    (``chain`` False: nor for any other loop that changes ``x`` between forwards there)."""
     rows = ROWS and PATCH_CHAIN and den.fused and torch.device(device).type == "cuda"
     if rows and (not eta or (den.P.folded and fold_width_ok(model.embed_dim))):
         return _Rows(model, N, device, den)
-    return _Image(model, N, device, den, x, x0, chain=not eta)
+    return _Image(model, N, device, den, x, x0, chain=chain and not eta)
 
 
 def _ddim_step(s, coef, each: bool, nz):
@@ -271,6 +285,10 @@ class _StepNoise:
     def site(self, i: int):
         return (self.rng, ops.SITE_STEP_NOISE + i)
 
+    def repaint_sites(self, n: int):
+        """(paste site, jump site) of an inpainting loop's forward ``n``."""
+        return ops.SITE_PASTE_NOISE + n, ops.SITE_JUMP_NOISE + n
+
     def set_seed(self, seed: int):
         self.rng.copy_(torch.tensor([int(seed), 0], dtype=torch.int64))
 
@@ -307,10 +325,11 @@ class _LoopState:
     """One cached loop: its static buffers (``x`` in, ``x0`` / ``traj`` / ``x`` out), the
     :class:`_StepNoise` of a stochastic one, the :class:`_GraphLoop`, and ``key`` = what the
     capture depends on (:meth:`_Denoiser.key_of` when it was built)."""
-    __slots__ = ("key", "x", "x0", "traj", "noise", "loop")
+    __slots__ = ("key", "x", "x0", "traj", "noise", "loop", "known", "mask")
 
-    def __init__(self, key, x, loop, x0=None, traj=None, noise=None):
+    def __init__(self, key, x, loop, x0=None, traj=None, noise=None, known=None, mask=None):
         self.key, self.x, self.x0, self.traj, self.noise, self.loop = key, x, x0, traj, noise, loop
+        self.known, self.mask = known, mask  # an inpainting loop's patch rows to keep / their uint8 mask
 
 
 def _cached_loop(model, key, build, limit: Optional[int] = None) -> _LoopState:
@@ -740,3 +759,97 @@ def img2img_noised(draft: torch.Tensor, eps: torch.Tensor, starts: Sequence[int]
     (ViT_draft2drawing.py:395-396)."""
     alpha = torch.tensor([img2img_alpha(s, total_steps) for s in starts], device=draft.device).view(-1, 1, 1, 1)
     return torch.sqrt(1 - alpha) * eps + torch.sqrt(alpha) * draft
+
+
+INPAINT_GRAPHS = 8  # cached inpainting loops (graph + buffers) per model
+
+
+def _inpaint_mask(mask, B: int, C: int, H: int, W: int) -> torch.Tensor:
+    """``mask`` (bool, or numeric binarised at > 0.5; 1 = keep) as a host bool [B, C, H, W]."""
+    mask = torch.as_tensor(mask).detach().cpu()
+    keep = mask if mask.dtype == torch.bool else mask.float() > 0.5
+    if tuple(keep.shape) == (H, W):
+        keep = keep.view(1, 1, H, W)
+    elif tuple(keep.shape) not in ((B, 1, H, W), (B, C, H, W)):
+        raise ValueError(f"mask must be [{H}, {W}], [{B}, 1, {H}, {W}] or [{B}, {C}, {H}, {W}], "
+                         f"got {tuple(mask.shape)}")
+    return keep.expand(B, C, H, W)
+
+
+def _inpaint_state(model, B: int, k: int, eta: float, resample: int, device) -> _LoopState:
+    """Buffers + loop of :func:`inpaint`: forward n is one head step with row ``n // resample``
+    of the DDIM table (noise site ``n`` at eta > 0) and one mask step with row n of
+    :func:`schedule.repaint_table`."""
+    T = model.total_steps
+    ts, rp = repaint_table(T, k, resample, device=device)
+    if len(ts) >= ops.SITE_LOOP_FORWARDS:
+        raise ValueError(f"inpaint: {len(ts)} forwards (k={k}, resample={resample}); a loop has noise sites for "
+                         f"fewer than {ops.SITE_LOOP_FORWARDS}")
+    den = _Denoiser(model, device)
+    coef = ddim_table_eta(T, k, eta, device=device)[1] if eta > 0 else ddim_table(T, k, device=device)[1]
+    coef = coef.repeat_interleave(resample, 0).contiguous()  # one row per forward
+    x = torch.zeros(B, model.in_chans, *model.img_size, device=device)
+    tt = _step_times(ts, B, device)
+    nz = _StepNoise(model, B, device)  # (the paste draws noise at every eta)
+    known = torch.zeros(nz.rows, device=device)
+    mask = torch.zeros(nz.rows, dtype=torch.uint8, device=device)
+    s = _loop_state(model, B, device, den, x, eta=eta > 0, chain=False)
+    step = _ddim_step(s, coef, False, nz if eta > 0 else None)
+
+    def loop():
+        s.begin(x)
+        for n in range(len(ts)):
+            step(n, tt[n])  # the DDIM jump t -> t-k in the head epilogue
+            s.repaint(known, mask, rp[n], nz.rng, *nz.repaint_sites(n))  # paste (+ jump back to t)
+        s.write_back(x=x)
+
+    return _LoopState(den.key(), x, _GraphLoop(loop, device), noise=nz, known=known, mask=mask)
+
+
+@torch.no_grad()
+def inpaint(model, image: torch.Tensor, mask, k: int = 10, eta: float = 0.0, resample: int = 1, device=None,
+            generator: Optional[torch.Generator] = None, use_graph: bool = True,
+            noise: Optional[torch.Tensor] = None, noise_seed: Optional[int] = None, unit: bool = True) -> torch.Tensor:
+    """Mask-conditioned DDIM sampling: keep ``image`` where ``mask`` is 1, generate the rest
+    (RePaint, Lugmayr et al. 2022; no retraining of an x0-predicting model).
+
+    From x_T, every step t of the ``ddim_timesteps(T, k)`` grid is one forward with the usual
+    head step (``eta`` as in :class:`DDIMSampler`) followed by one :func:`ops.repaint_rows_`
+    launch, which replaces the kept elements by the image noised to the level t-k the step
+    landed on.  ``resample`` > 1 (an int >= 1) runs each grid step that many times, the mask
+    step diffusing the state forward to level t again after every run but the last, which lets
+    the generated region harmonise with the kept one.
+
+    ``image`` [B,C,H,W] or [C,H,W] in [-1, 1]; ``mask`` bool or numeric (binarised at > 0.5),
+    [H,W], [B,1,H,W] or [B,C,H,W].  x_T is ``noise`` or one ``torch.normal`` draw from
+    ``generator``; the seed of the paste / jump / step noise one :func:`draw_noise_seed` after
+    it (``noise_seed=`` overrides it).  The loop is one hipGraph cached per (B, k, eta,
+    resample), at most ``INPAINT_GRAPHS`` per model; image, mask, x_T and the seed are static
+    buffers, so a new one of any of them is a replay.
+
+    Returns the final state -- at the last step x0-hat in the free region and ``image`` exactly
+    in the kept one -- as host images in [0, 1] (``unit=False``: in [-1, 1])."""
+    device = torch.device(device) if device is not None else next(model.parameters()).device
+    T = model.total_steps
+    C, (H, W), p = model.in_chans, model.img_size, model.patch_size
+    if image.dim() == 3:
+        image = image.unsqueeze(0)
+    if image.dim() != 4 or tuple(image.shape[1:]) != (C, H, W):
+        raise ValueError(f"image must be [B, {C}, {H}, {W}] or [{C}, {H}, {W}], got {tuple(image.shape)}")
+    B = image.shape[0]
+    if isinstance(resample, bool) or not isinstance(resample, int) or resample < 1:
+        raise ValueError(f"resample must be an int >= 1, got {resample!r}")
+    eta = float(eta)
+    ddim_coefficients_eta(T, T - 1, k, eta)  # (ValueError for eta outside [0, 1])
+    keep = _inpaint_mask(mask, B, C, H, W)
+    key = ("inpaint", B, k, eta, resample, str(device))
+    st = _cached_loop(model, key, lambda: _inpaint_state(model, B, k, eta, resample, device), INPAINT_GRAPHS)
+    st.known.copy_(ops.image_to_rows(image.detach().float().cpu(), p))
+    st.mask.copy_(ops.image_to_rows(keep.to(torch.uint8), p))
+    if noise is not None:
+        st.x.copy_(noise)
+    else:
+        st.x.copy_(torch.normal(0.0, 1.0, (B, C, H, W), generator=generator))
+    st.noise.set_seed(draw_noise_seed(generator) if noise_seed is None else noise_seed)
+    st.loop.run(use_graph and device.type == "cuda")
+    return _unit_host(st.x) if unit else st.x.cpu().clone()

@@ -96,6 +96,39 @@ def ddim_table_eta(total_steps: int, k: int, eta: float, start: int | None = Non
     return ts, coef
 
 
+def repaint_row(total_steps: int, t: int, k: int, jump: bool):
+    """``(ka, kb, ra, rb)`` of the inpainting mask step after the DDIM jump t -> t-k
+    (``ops.repaint_rows_``; Lugmayr et al. 2022).  The known region is pasted at the level the
+    jump landed on, ``ka known + kb z1`` with ``ka, kb = sqrt(a_{t-k}), sqrt(1 - a_{t-k})``: the
+    very floats :func:`ddim_coefficients` returns last (exactly 1.0, 0.0 when the jump lands on
+    a_{t-k} = 1).  ``jump``: the state is then diffused forward to level t again, ``ra x + rb
+    z2`` with ``ra, rb = sqrt(a_t / a_{t-k}), sqrt(1 - a_t / a_{t-k})`` and the ``a_t`` of
+    :func:`ddim_coefficients` (its 1e-5 included); otherwise ``ra, rb = 1.0, 0.0``."""
+    _, _, ka, kb = ddim_coefficients(total_steps, t, k)
+    a_t = 1.0 - math.sqrt((t + 1) / total_steps) + 1e-5
+    a_tk = 1.0 - math.sqrt((t + 1 - k) / total_steps)
+    if a_t > a_tk:
+        raise ValueError(f"invalid DDIM jump t={t}, k={k}: a_t > a_(t-k)")
+    if not jump:
+        return ka, kb, 1.0, 0.0
+    r = a_t / a_tk
+    return ka, kb, math.sqrt(r), math.sqrt(1.0 - r)
+
+
+def repaint_table(total_steps: int, k: int, resample: int = 1, device="cpu"):
+    """``(ts, [forwards, 4] fp32 rows of :func:`repaint_row`)`` of an inpainting loop: each
+    step of the ``ddim_timesteps(total_steps, k)`` grid runs ``resample`` times, jumping back to
+    its own level after every run but the last; ``ts`` lists the timestep of every forward."""
+    if isinstance(resample, bool) or not isinstance(resample, int) or resample < 1:
+        raise ValueError(f"resample must be an int >= 1, got {resample!r}")
+    ts, rows = [], []
+    for t in ddim_timesteps(total_steps, k):
+        for j in range(resample):
+            ts.append(t)
+            rows.append(repaint_row(total_steps, t, k, jump=j < resample - 1))
+    return ts, torch.tensor(rows, dtype=torch.float32, device=device)
+
+
 def img2img_alpha(t_start: int, total_steps: int) -> float:
     return 1.0 - math.sqrt(t_start / total_steps)
 

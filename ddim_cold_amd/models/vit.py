@@ -340,6 +340,13 @@ class DiffusionVisionTransformer(nn.Module):
         return DDIMSampler(self, device, k=k, use_graph=use_graph, eta=eta).sample(N, generator=generator,
                                                                                      verbose=verbose)
 
+    def inpaint(self, image, mask, k=10, eta=0.0, resample=1, device=None, generator=None, use_graph=True, **kw):
+        """Keep ``image`` where ``mask`` is 1 and generate the rest
+        (:func:`ddim_cold_amd.diffusion.samplers.inpaint`); returns CPU images in [0, 1]."""
+        from ..diffusion.samplers import inpaint
+        return inpaint(self, image, mask, k=k, eta=eta, resample=resample, device=device, generator=generator,
+                       use_graph=use_graph, **kw)
+
     @torch.no_grad()
     def diffusion_sequence(self, device, k=100, N=5, generator=None, eta=0.0):
         """DDIM trajectory recorder (`ViT.py:239-256`): [x_T, x0_hat_1, ...] on CPU (``eta``

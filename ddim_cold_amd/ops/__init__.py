@@ -24,6 +24,7 @@ __all__ = [
     "sqnorm", "adamw_step", "weight_ema_decay", "advance_counters", "ddim_step", "ddim_step_", "randn_", "q_sample",
     "pixelate_pair", "cold_batch", "gauss_batch", "batch_draw", "BatchSource", "head_step_rows_", "cold_step_", "cold_step_rows_",
     "image_to_rows", "rows_to_image", "embed_weight_rows", "patch_embed_cold_fwd", "ln_fold_", "SITE_STEP_NOISE",
+    "repaint_rows_", "SITE_PASTE_NOISE", "SITE_JUMP_NOISE", "SITE_LOOP_FORWARDS",
     "HEAD_DDIM", "HEAD_CLAMP", "HEAD_DDIM_EACH", "HEAD_ETA", "HEAD_ETA_EACH",
 ]
 
@@ -260,6 +261,12 @@ def embed_weight_rows(w_pe, C: int, patch: int):
 # noise site of sampling step i (0-based from the top of the grid): SITE_STEP_NOISE + i, clear
 # of the model's sites (1, 16 + 8 block + 0..5) and the data sites (3, 4)
 SITE_STEP_NOISE = 4096
+# inpainting (repaint_rows_): forward n of a loop pastes the known region with the noise of site
+# SITE_PASTE_NOISE + n and jumps back with that of SITE_JUMP_NOISE + n; the three ranges are 4096
+# apart, so a loop has fewer than SITE_LOOP_FORWARDS forwards
+SITE_PASTE_NOISE = 8192
+SITE_JUMP_NOISE = 12288
+SITE_LOOP_FORWARDS = 4096
 # head-step modes (the values csrc/bindings.cpp and csrc/gemm_epi.h test): clamp + DDIM update
 # with one coefficient row / clamp only / DDIM with one row per sample / the stochastic
 # (eta > 0) DDIM step with one row of 8 / with one row of 8 per sample
@@ -827,6 +834,24 @@ def cold_step_rows_(x, x0, t, batch: int, C: int, H: int, W: int, patch: int, al
     xi, x0i = (rows_to_image(v, batch, C, H, W, patch) for v in (x, x0))
     x.copy_(image_to_rows(ref.cold_step(xi, x0i, t, algorithm), patch))
     _cold_rows_out(patches_out, x.to(torch.bfloat16), t, batch)
+
+
+def repaint_rows_(x, known, mask, coef, rng, site_paste: int, site_jump: int, patches_out=None):
+    """Mask step of inpainting (RePaint), in place on the sampler's fp32 patch rows ``x`` [B*P, F]
+    (:func:`reference.repaint_rows`): where ``mask`` (uint8, same shape) is non-zero ``x <- ka
+    known + kb z1``, then, unless ``{ra, rb}`` is ``{1, 0}``, ``x <- ra x + rb z2`` everywhere.
+    ``coef`` a device fp32 ``{ka, kb, ra, rb}`` (``schedule.repaint_row``), ``z1`` / ``z2`` =
+    :func:`randn_` over a buffer like ``x`` at ``(rng, site_paste)`` / ``(rng, site_jump)``, ``rng``
+    an int64[2] ``{seed, 0}``.  ``patches_out`` (bf16, same shape): the bf16 of every element
+    written; a paste-only call writes nothing where four consecutive mask bytes are zero."""
+    if _hip(x):
+        return _ops().repaint_rows_(x, known, mask, coef, rng, int(site_paste), int(site_jump), patches_out)
+    if min(int(site_paste), int(site_jump)) < 0:
+        raise ValueError("repaint_rows_: noise sites must be non-negative")
+    out, wrote = ref.repaint_rows(x, known, mask, coef, rng, int(site_paste), int(site_jump))
+    x.copy_(out)
+    if patches_out is not None:
+        patches_out[wrote] = out.to(torch.bfloat16)[wrote]
 
 
 def randn_(out, rng, site: int):

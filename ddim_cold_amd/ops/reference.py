@@ -463,6 +463,43 @@ def ddim_step_eta(x_t, x0_raw, coef8, z):
     return c2 * x0 + cd * eps + sg * z, x0
 
 
+def _fma32(a, b, c):
+    """fp32 ``fma(a, b, c)`` of fp32 operands: the product is exact in fp64, the sum rounded once
+    to fp64 and once to fp32 (equal to the fused result except in rare double-rounding ties)."""
+    return (a.double() * b.double() + c.double()).float()
+
+
+def repaint_rows(x, known, mask, coef, rng, site_paste: int, site_jump: int):
+    """Mask step of inpainting (RePaint, Lugmayr et al. 2022) on the fp32 patch-row state ``x``
+    [B*P, F], the arithmetic of ``repaint_rows_kernel`` with its roundings:
+
+        ``y   = mask ? fma(kb, z1, fl(ka known)) : x``
+        ``out = (ra == 1 and rb == 0) ? y : fma(rb, z2, fl(ra y))``
+
+    ``coef`` = fp32 ``{ka, kb, ra, rb}``; ``z1`` / ``z2`` = ``ops.randn_`` over a buffer like ``x`` at
+    ``(rng, site_paste)`` / ``(rng, site_jump)``.  Returns ``(out, wrote)``: ``wrote`` marks the
+    elements the kernel stores -- all of them after a jump, else the 4-vectors (of the flat
+    index) with a mask byte set."""
+    from . import randn_
+    if x.numel() % 4:
+        raise ValueError("repaint_rows: the element count must be a multiple of 4")
+    if known.shape != x.shape or mask.shape != x.shape or coef.numel() != 4:
+        raise ValueError("repaint_rows: x, known and mask of one shape, coef of 4 floats")
+    ka, kb, ra, rb = coef.detach().float().cpu().reshape(4)
+    keep = mask != 0
+    y = x.clone()
+    if bool(keep.any()):
+        z1 = torch.empty_like(x)
+        randn_(z1, rng, site_paste)
+        y = torch.where(keep, _fma32(kb, z1, ka * known), x)
+    if float(ra) == 1.0 and float(rb) == 0.0:
+        wrote = keep.reshape(-1, 4).any(dim=1, keepdim=True).expand(-1, 4).reshape(x.shape)
+        return y, wrote
+    z2 = torch.empty_like(x)
+    randn_(z2, rng, site_jump)
+    return _fma32(rb, z2, ra * y), torch.ones_like(keep)
+
+
 def pixelate(img, factor: int):
     """NEAREST down to floor(W/f) then NEAREST up (`diffusion_loader.py:79-83`)."""
     H, W = img.shape[-2:]
