@@ -32,6 +32,9 @@ constexpr auto F32 = at::kFloat;
 constexpr auto BF16 = at::kBFloat16;
 constexpr auto I64 = at::kLong;
 
+// an optional tensor argument that was passed
+bool given(const c10::optional<Tensor>& t) { return t.has_value() && t->defined(); }
+
 void check_rng(const Tensor& rng) {
   CHECK_IN(rng, I64);
   TORCH_CHECK(rng.numel() >= 2, "rng must hold {seed, step}");
@@ -61,17 +64,17 @@ bool ln_fold_width_ok(int64_t D) { return D % 32 == 0 && D / 32 <= 16; }
 // b = bias + W beta; ln_st [M][2] row {sum, sum^2} of x; ln_c [N] row sums of w
 void apply_fold(GemmArgs& g, int M, int N, const c10::optional<Tensor>& ln_st, const c10::optional<Tensor>& ln_c,
                 double eps, const c10::optional<Tensor>& ln_mean, const c10::optional<Tensor>& ln_rstd) {
-  if (!ln_st.has_value() || !ln_st->defined()) return;
+  if (!given(ln_st)) return;
   CHECK_IN((*ln_st), F32);
-  TORCH_CHECK(ln_c.has_value() && ln_c->defined(), "LayerNorm fold needs ln_c");
+  TORCH_CHECK(given(ln_c), "LayerNorm fold needs ln_c");
   CHECK_IN((*ln_c), F32);
   TORCH_CHECK(ln_fold_width_ok(g.K), "LayerNorm fold: width must be a multiple of 32, <= 512");
   TORCH_CHECK(ln_st->numel() == 2 * (int64_t)M * (g.K / 32) && ln_c->numel() == N, "LayerNorm fold shapes");
   g.ln_st = ln_st->data_ptr<float>();
   g.ln_c = ln_c->data_ptr<float>();
   g.ln_eps = (float)eps;
-  if (ln_mean.has_value() && ln_mean->defined()) {
-    TORCH_CHECK(ln_rstd.has_value() && ln_rstd->defined(), "ln_mean needs ln_rstd");
+  if (given(ln_mean)) {
+    TORCH_CHECK(given(ln_rstd), "ln_mean needs ln_rstd");
     CHECK_IN((*ln_mean), F32); CHECK_IN((*ln_rstd), F32);
     TORCH_CHECK(ln_mean->numel() == M && ln_rstd->numel() == M, "ln_mean / ln_rstd shapes");
     g.ln_mean = ln_mean->data_ptr<float>();
@@ -82,9 +85,9 @@ void apply_fold(GemmArgs& g, int M, int N, const c10::optional<Tensor>& ln_st, c
 // LayerNorm fold, producer side: row statistics (accumulated, zeroed beforehand) + bf16 copy
 void apply_prod(GemmArgs& g, int64_t rows, int64_t D, const c10::optional<Tensor>& st_out,
                 const c10::optional<Tensor>& xb_out) {
-  if (!st_out.has_value() || !st_out->defined()) return;
+  if (!given(st_out)) return;
   CHECK_IN((*st_out), F32);
-  TORCH_CHECK(xb_out.has_value() && xb_out->defined(), "row statistics need the bf16 copy output");
+  TORCH_CHECK(given(xb_out), "row statistics need the bf16 copy output");
   CHECK_IN((*xb_out), BF16);
   TORCH_CHECK(ln_fold_width_ok(D), "LayerNorm fold: width must be a multiple of 32, <= 512");
   TORCH_CHECK(st_out->numel() == 2 * rows * (D / 32) && xb_out->numel() == rows * D, "LayerNorm-fold producer shapes");
@@ -115,7 +118,7 @@ static std::tuple<Tensor, Tensor> patch_embed_impl(Tensor img, Tensor t, Tensor 
   auto x = at::empty({B, N, D}, img.options());
   // patches_in: the patch rows are already there (a sampler step's head wrote them);
   // the GEMM epilogue then writes the cls rows and no patchify launch is needed
-  const bool have_patches = patches_in.has_value() && patches_in->defined();
+  const bool have_patches = given(patches_in);
   if (have_patches) {
     CHECK_IN((*patches_in), BF16);
     TORCH_CHECK(patches_in->numel() == (int64_t)B * NP * F, "patches_in must be [B*P, C*p*p]");
@@ -124,11 +127,11 @@ static std::tuple<Tensor, Tensor> patch_embed_impl(Tensor img, Tensor t, Tensor 
   auto patches = have_patches ? *patches_in : at::empty({(int64_t)B * NP, F}, img.options().dtype(BF16));
   float* st = nullptr;
   void* xb = nullptr;
-  if (ln_st.has_value() && ln_st->defined()) {
+  if (given(ln_st)) {
     CHECK_IN((*ln_st), F32);
     TORCH_CHECK(ln_fold_width_ok(D), "LayerNorm fold: width must be a multiple of 32, <= 512");
     TORCH_CHECK(ln_st->numel() == (int64_t)B * N * (D / 32) * 2, "ln_st must be [B*N, D/32, 2]");
-    TORCH_CHECK(xb_out.has_value() && xb_out->defined(), "ln_st needs xb_out");
+    TORCH_CHECK(given(xb_out), "ln_st needs xb_out");
     CHECK_IN((*xb_out), BF16);
     TORCH_CHECK(xb_out->numel() == (int64_t)B * N * D, "xb_out shape");
     st = ln_st->data_ptr<float>();
@@ -182,7 +185,7 @@ ColdSrc batch_source(const Tensor& pool, const Tensor& img, const Tensor& target
   cs.pool = pool.data_ptr<float>(); cs.pool_n = pool.size(0);
   cs.idx = idx.data_ptr<int64_t>(); cs.draw_idx = draw_idx;
   cs.t_out = t.data_ptr<int64_t>(); cs.target = target.data_ptr<float>();
-  if (ctr.has_value() && ctr->defined()) {
+  if (given(ctr)) {
     CHECK_IN((*ctr), I64);
     TORCH_CHECK(ctr->device() == dev && ctr->numel() >= 1, what, ": step counter");
     TORCH_CHECK(!draw_idx, what, ": a stepped index table is read, not drawn");
@@ -256,7 +259,7 @@ Tensor linear_fwd(Tensor a, Tensor w, c10::optional<Tensor> b, bool out_fp32, c1
   auto out = at::empty({M, Dout}, a.options().dtype(out_fp32 ? at::kFloat : at::kBFloat16));
   GemmArgs g = nt_args(a2, w);
   g.C = out.data_ptr(); g.ldc = Dout;
-  if (b.has_value() && b->defined()) {
+  if (given(b)) {
     CHECK_IN((*b), F32);
     TORCH_CHECK(b->numel() == Dout, "bias shape");
     g.bias = b->data_ptr<float>();
@@ -290,7 +293,7 @@ std::vector<int64_t> gemm_plan_op(int64_t epi, bool at, bool bt, int64_t M, int6
 }
 // GEMM phase stamps (tools/ub_gemm_stamps.py): an int32 buffer, or None to stop
 void gemm_stamps_op(c10::optional<Tensor> buf) {
-  if (buf.has_value() && buf->defined()) {
+  if (given(buf)) {
     TORCH_CHECK(buf->is_cuda() && buf->scalar_type() == at::kInt && buf->is_contiguous(), "gemm_stamps: int32 cuda");
     gemm_set_stamps(reinterpret_cast<uint32_t*>(buf->data_ptr<int32_t>()));
   } else {
@@ -387,58 +390,83 @@ std::tuple<Tensor, Tensor> linear_gelu_fwd(Tensor a, Tensor w, Tensor b, Tensor 
   return {u, h};
 }
 
+// The GEMM of the four head ops (each: build it, add its own fields, apply_fold, launch):
+// a [B*(np + 1)][K] token rows (np patches per sample after the cls row), w [F][K], b [F],
+// checked against each other; operands, bias, tokens and batch filled (M = B*(np + 1), N = F).
+GemmArgs head_gemm(const Tensor& a, const Tensor& w, const Tensor& b, int64_t B, int64_t np, int64_t F,
+                   const char* what) {
+  const int K = a.size(-1);
+  auto a2 = a.view({-1, K});
+  check_linear(a2, w, K);
+  TORCH_CHECK(a2.size(0) == B * (np + 1) && w.size(0) == F && b.numel() == F, what);
+  GemmArgs g = nt_args(a2, w);
+  g.bias = b.data_ptr<float>();
+  g.tokens = np + 1; g.batch = B;
+  return g;
+}
+// ... of a [B,C,H,W] image in patch x patch tiles (EPI_HEAD; EPI_HEADL reads only tokens / batch)
+GemmArgs head_gemm(const Tensor& a, const Tensor& w, const Tensor& b, int64_t B, int64_t C, int64_t H, int64_t W,
+                   int64_t patch, const char* what) {
+  GemmArgs g = head_gemm(a, w, b, B, (H / patch) * (W / patch), C * patch * patch, what);
+  g.chans = C; g.img_h = H; g.img_w = W; g.patch = patch;
+  return g;
+}
+// ... of the patch rows x [B*P][F] (EPI_HEADR / EPI_HEADRS: 16-byte accesses, so F % 4 == 0)
+GemmArgs head_gemm(const Tensor& a, const Tensor& w, const Tensor& b, int64_t B, const Tensor& x) {
+  TORCH_CHECK(B >= 1 && x.dim() == 2 && x.size(0) % B == 0 && x.size(1) % 4 == 0, "x must be [B*P, F], F % 4 == 0");
+  return head_gemm(a, w, b, B, x.size(0) / B, x.size(1), "head rows shapes: a [B*(P+1), K], w [F, K], b [F] for x [B*P, F]");
+}
+
+// The step outputs of the DDIM head modes, in either layout: x0_out and coef passed, fp32, x0_out
+// shaped like x, and the mode's coefficient rows.  Fills res (x_t = x, updated in place), C2, coef.
+void step_outputs(GemmArgs& g, const Tensor& x, const c10::optional<Tensor>& x0_out,
+                  const c10::optional<Tensor>& coef, int64_t mode) {
+  TORCH_CHECK(given(x0_out) && given(coef), "head step: modes 1 / 4 / 5 / 6 (ddim) need x0_out and coef");
+  CHECK_IN((*x0_out), F32); CHECK_IN((*coef), F32);
+  TORCH_CHECK(x0_out->sizes() == x.sizes(), "head step: x0_out must have x's shape");
+  const int64_t rows = mode == HEAD_DDIM_EACH || mode == HEAD_ETA_EACH ? g.batch : 1;
+  const bool noisy = mode == HEAD_ETA || mode == HEAD_ETA_EACH;
+  TORCH_CHECK(noisy ? coef->numel() == 8 * rows : coef->numel() >= 4 * rows,
+              "head step: coefficient rows of 4 floats for modes 1 / 4 (mode 1: >= 4, mode 4: >= 4 * B), of 8 for "
+              "modes 5 / 6 (mode 5: 8, mode 6: 8 * B)");
+  g.res = x.data_ptr<float>(); g.C2 = x0_out->data_ptr(); g.coef = coef->data_ptr<float>();
+}
+
 Tensor head_fwd(Tensor a, Tensor w, Tensor b, int64_t B, int64_t C, int64_t H, int64_t W, int64_t patch,
                 c10::optional<Tensor> ln_st, c10::optional<Tensor> ln_c, double ln_eps, c10::optional<Tensor> ln_mean, c10::optional<Tensor> ln_rstd) {
   CHECK_IN(a, BF16); CHECK_IN(w, BF16); CHECK_IN(b, F32);
   const c10::DeviceGuard guard(a.device());
-  const int K = a.size(-1);
-  auto a2 = a.view({-1, K});
-  check_linear(a2, w, K);
-  const int N = (H / patch) * (W / patch) + 1;
-  TORCH_CHECK(a2.size(0) == B * N && w.size(0) == C * patch * patch && b.numel() == w.size(0), "head shapes");
+  GemmArgs g = head_gemm(a, w, b, B, C, H, W, patch, "head shapes");
+  apply_fold(g, g.M, g.N, ln_st, ln_c, ln_eps, ln_mean, ln_rstd);
   auto img = at::empty({B, C, H, W}, a.options().dtype(F32));
-  GemmArgs g = nt_args(a2, w);
-  g.C = img.data_ptr(); g.bias = b.data_ptr<float>();
-  g.tokens = N; g.batch = B; g.chans = C; g.img_h = H; g.img_w = W; g.patch = patch;
-  apply_fold(g, B * N, w.size(0), ln_st, ln_c, ln_eps, ln_mean, ln_rstd);
+  g.C = img.data_ptr();
   gemm_nt(g, EPI_HEAD, cur_stream());
   return img;
 }
 
 // Head GEMM with the sampler step fused into its unpatchify epilogue:
-//   mode 1 (DDIM): x0 = clamp(head(a), -1, 1); x <- sqrt(a_tk) x0 + sqrt(1-a_tk) (x - sqrt(a_t) x0)/sqrt(1-a_t)
+//   mode 1 (HEAD_DDIM): x0 = clamp(head(a), -1, 1); x <- sqrt(a_tk) x0 + sqrt(1-a_tk) (x - sqrt(a_t) x0)/sqrt(1-a_t)
 //                  in place, x0 written to x0_out; coef = device row {sqrt a_t, sqrt 1-a_t, sqrt a_tk, sqrt 1-a_tk}
-//   mode 2 (cold): x <- clamp(head(a), -1, 1)
-//   mode 4 (img2img): mode 1 with one coefficient row per sample (coef [B][4])
+//   mode 2 (HEAD_CLAMP, cold): x <- clamp(head(a), -1, 1)
+//   mode 4 (HEAD_DDIM_EACH, img2img): mode 1 with one coefficient row per sample (coef [B][4])
 void head_step_(Tensor a, Tensor w, Tensor b, Tensor x, c10::optional<Tensor> x0_out, c10::optional<Tensor> coef,
                 int64_t patch, int64_t mode, c10::optional<Tensor> ln_st, c10::optional<Tensor> ln_c, double ln_eps,
                 c10::optional<Tensor> patches_out) {
   CHECK_IN(a, BF16); CHECK_IN(w, BF16); CHECK_IN(b, F32); CHECK_IN(x, F32);
   const c10::DeviceGuard guard(a.device());
   TORCH_CHECK(x.dim() == 4, "x must be [B, C, H, W]");
-  const int B = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
-  const int K = a.size(-1);
-  auto a2 = a.view({-1, K});
-  check_linear(a2, w, K);
-  const int N = (H / patch) * (W / patch) + 1;
-  TORCH_CHECK(a2.size(0) == B * N && w.size(0) == C * patch * patch && b.numel() == w.size(0), "head shapes");
-  TORCH_CHECK(mode == 1 || mode == 2 || mode == 4, "head_step_: mode 1 (ddim), 2 (clamp) or 4 (per-sample ddim)");
-  GemmArgs g = nt_args(a2, w);
-  g.C = x.data_ptr(); g.bias = b.data_ptr<float>();
-  g.tokens = N; g.batch = B; g.chans = C; g.img_h = H; g.img_w = W; g.patch = patch;
+  GemmArgs g = head_gemm(a, w, b, x.size(0), x.size(1), x.size(2), x.size(3), patch, "head shapes");
+  TORCH_CHECK(mode == HEAD_DDIM || mode == HEAD_CLAMP || mode == HEAD_DDIM_EACH,
+              "head_step_: mode 1 (ddim), 2 (clamp) or 4 (per-sample ddim)");
+  g.C = x.data_ptr();
   g.head_mode = (int)mode;
-  if (mode == 1 || mode == 4) {
-    TORCH_CHECK(x0_out.has_value() && coef.has_value(), "ddim mode needs x0_out and coef");
-    CHECK_IN((*x0_out), F32); CHECK_IN((*coef), F32);
-    TORCH_CHECK(x0_out->sizes() == x.sizes() && coef->numel() >= (mode == 4 ? 4 * B : 4), "x0_out / coef shapes");
-    g.res = x.data_ptr<float>(); g.C2 = x0_out->data_ptr(); g.coef = coef->data_ptr<float>();
-  }
-  if (patches_out.has_value() && patches_out->defined()) {  // the next step's patch rows
+  if (mode != HEAD_CLAMP) step_outputs(g, x, x0_out, coef, mode);
+  if (given(patches_out)) {  // the next step's patch rows
     CHECK_IN((*patches_out), BF16);
-    TORCH_CHECK(patches_out->numel() == (int64_t)B * (N - 1) * C * patch * patch, "patches_out must be [B*P, C*p*p]");
+    TORCH_CHECK(patches_out->numel() == (int64_t)g.batch * (g.tokens - 1) * g.N, "patches_out must be [B*P, C*p*p]");
     g.patch_out = patches_out->data_ptr();
   }
-  apply_fold(g, B * N, w.size(0), ln_st, ln_c, ln_eps, c10::nullopt, c10::nullopt);
+  apply_fold(g, g.M, g.N, ln_st, ln_c, ln_eps, c10::nullopt, c10::nullopt);
   gemm_nt(g, EPI_HEAD, cur_stream());
 }
 
@@ -451,51 +479,33 @@ void head_step_rows_(Tensor a, Tensor w, Tensor b, Tensor x, c10::optional<Tenso
                      c10::optional<Tensor> rng, int64_t noise_site) {
   CHECK_IN(a, BF16); CHECK_IN(w, BF16); CHECK_IN(b, F32); CHECK_IN(x, F32);
   const c10::DeviceGuard guard(a.device());
-  const int K = a.size(-1);
-  auto a2 = a.view({-1, K});
-  check_linear(a2, w, K);
-  const int F = w.size(0), B = batch;
-  TORCH_CHECK(B >= 1 && x.dim() == 2 && x.size(1) == F && x.size(0) % B == 0, "x must be [B*P, F]");
-  const int NP = x.size(0) / B, N = NP + 1;
-  TORCH_CHECK(a2.size(0) == (int64_t)B * N && b.numel() == F && F % 4 == 0, "head rows shapes");
-  // modes 5 / 6 (EPI_HEADRS): the stochastic DDIM step (eta > 0), x <- c2 x0 + dir (x - c0 x0) / c1 + sigma z
-  // from rows of 8 floats {c0, c1, c2, dir, sigma, 0, 0, 0} (5: one row, 6: one per sample); z = element
-  // (row, column) of randn_ over x at (rng, noise_site), drawn in the epilogue
-  const bool noisy = mode == 5 || mode == 6;
-  TORCH_CHECK(mode == 1 || mode == 2 || mode == 4 || noisy,
+  GemmArgs g = head_gemm(a, w, b, batch, x);
+  // modes 5 / 6 (HEAD_ETA / HEAD_ETA_EACH, EPI_HEADRS): the stochastic DDIM step (eta > 0), x <- c2 x0 +
+  // dir (x - c0 x0) / c1 + sigma z from rows of 8 floats {c0, c1, c2, dir, sigma, 0, 0, 0} (5: one row, 6: one
+  // per sample); z = element (row, column) of randn_ over x at (rng, noise_site), drawn in the epilogue
+  const bool noisy = mode == HEAD_ETA || mode == HEAD_ETA_EACH;
+  TORCH_CHECK(mode == HEAD_DDIM || mode == HEAD_CLAMP || mode == HEAD_DDIM_EACH || noisy,
               "head_step_rows_: mode 1 (ddim), 2 (clamp), 4 (per-sample ddim), 5 (ddim with noise) or 6 (per-sample, with noise)");
-  GemmArgs g = nt_args(a2, w);
-  g.C = x.data_ptr(); g.bias = b.data_ptr<float>();
-  g.tokens = N; g.batch = B;
+  g.C = x.data_ptr();
   g.head_mode = (int)mode;
-  if (mode == 1 || mode == 4) {
-    TORCH_CHECK(x0_out.has_value() && coef.has_value(), "ddim mode needs x0_out and coef");
-    CHECK_IN((*x0_out), F32); CHECK_IN((*coef), F32);
-    TORCH_CHECK(x0_out->sizes() == x.sizes() && coef->numel() >= (mode == 4 ? 4 * B : 4), "x0_out / coef shapes");
-    g.res = x.data_ptr<float>(); g.C2 = x0_out->data_ptr(); g.coef = coef->data_ptr<float>();
-  }
+  if (mode != HEAD_CLAMP) step_outputs(g, x, x0_out, coef, mode);
   if (noisy) {
-    TORCH_CHECK(x0_out.has_value() && coef.has_value(), "head_step_rows_: modes 5 / 6 need x0_out and coef");
-    TORCH_CHECK(rng.has_value() && rng->defined(), "head_step_rows_: modes 5 / 6 need rng ({seed, 0}) for the noise");
-    CHECK_IN((*x0_out), F32); CHECK_IN((*coef), F32); check_rng(*rng);
-    TORCH_CHECK(x0_out->sizes() == x.sizes(), "head_step_rows_: x0_out must have x's shape");
-    TORCH_CHECK(coef->numel() == (mode == 6 ? 8 * (int64_t)B : 8),
-                "head_step_rows_: modes 5 / 6 take coefficient rows of 8 floats (mode 5: 8, mode 6: 8 * B)");
+    TORCH_CHECK(given(rng), "head_step_rows_: modes 5 / 6 need rng ({seed, 0}) for the noise");
+    check_rng(*rng);
     TORCH_CHECK(x.numel() < (1LL << 31), "head_step_rows_: the noise index is 32-bit (B*P*F < 2^31)");
     TORCH_CHECK(noise_site >= 0 && noise_site < (1LL << 31), "head_step_rows_: noise_site out of range");
-    g.res = x.data_ptr<float>(); g.C2 = x0_out->data_ptr(); g.coef = coef->data_ptr<float>();
     g.rng = rng->data_ptr<int64_t>(); g.site_drop = (int)noise_site;
   }
-  if (patches_out.has_value() && patches_out->defined()) {
+  if (given(patches_out)) {
     CHECK_IN((*patches_out), BF16);
     TORCH_CHECK(patches_out->sizes() == x.sizes(), "patches_out must be [B*P, F]");
     g.patch_out = patches_out->data_ptr();
   }
-  apply_fold(g, B * N, F, ln_st, ln_c, ln_eps, c10::nullopt, c10::nullopt);
+  apply_fold(g, g.M, g.N, ln_st, ln_c, ln_eps, c10::nullopt, c10::nullopt);
   gemm_nt(g, noisy ? EPI_HEADRS : EPI_HEADR, cur_stream());
 }
 
-// Head GEMM with the training loss in its epilogue (head_mode 3): the smooth-L1
+// Head GEMM with the training loss in its epilogue (HEAD_LOSS): the smooth-L1
 // of the unpatchified prediction vs `target` (multi_gpu_trainer.py:124) as one
 // partial per workgroup, and its gradient written straight into the token
 // layout the head backward consumes (cls rows zero).  Returns (partials, dtok).
@@ -509,24 +519,17 @@ std::tuple<Tensor, Tensor> head_loss(Tensor a, Tensor w, Tensor b, Tensor target
   CHECK_IN(a, BF16); CHECK_IN(w, BF16); CHECK_IN(b, F32); CHECK_IN(target, F32);
   const c10::DeviceGuard guard(a.device());
   TORCH_CHECK(target.dim() == 4, "target must be [B, C, H, W]");
-  const int B = target.size(0), C = target.size(1), H = target.size(2), W = target.size(3);
-  const int K = a.size(-1);
-  auto a2 = a.view({-1, K});
-  check_linear(a2, w, K);
-  const int N = (H / patch) * (W / patch) + 1, F = C * patch * patch;
-  TORCH_CHECK(a2.size(0) == (int64_t)B * N && w.size(0) == F && b.numel() == F, "head_loss shapes");
+  GemmArgs g = head_gemm(a, w, b, target.size(0), target.size(1), target.size(2), target.size(3), patch,
+                         "head_loss shapes");
   TORCH_CHECK(beta > 0, "smooth-L1 beta must be > 0");
-  const int M = B * N;
-  auto dtok = at::empty({M, F}, a.options());
-  auto parts = at::empty({gemm_nt_grid(M, F, K)}, a.options().dtype(F32));
-  GemmArgs g = nt_args(a2, w);
-  g.C = dtok.data_ptr(); g.C2 = dtok.data_ptr(); g.bias = b.data_ptr<float>(); g.res = target.data_ptr<float>();
-  g.tokens = N; g.batch = B; g.chans = C; g.img_h = H; g.img_w = W; g.patch = patch;
-  g.head_mode = 3;
+  apply_fold(g, g.M, g.N, ln_st, ln_c, ln_eps, ln_mean, ln_rstd);
+  auto dtok = at::empty({g.M, g.N}, a.options());
+  auto parts = at::empty({gemm_nt_grid(g.M, g.N, g.K)}, a.options().dtype(F32));
+  g.C = dtok.data_ptr(); g.C2 = dtok.data_ptr(); g.res = target.data_ptr<float>();
+  g.head_mode = HEAD_LOSS;
   g.loss_beta = (float)beta;
-  g.loss_inv_n = 1.0f / (float)((int64_t)B * C * H * W);
+  g.loss_inv_n = 1.0f / (float)target.numel();
   g.loss_parts = parts.data_ptr<float>();
-  apply_fold(g, M, F, ln_st, ln_c, ln_eps, ln_mean, ln_rstd);
   gemm_nt(g, target_rows ? EPI_HEADL : EPI_HEAD, cur_stream());
   return {parts, dtok};
 }
@@ -537,8 +540,8 @@ std::tuple<Tensor, Tensor> smooth_l1_fwd_bwd(Tensor pred, Tensor target, int64_t
   CHECK_IN(pred, F32); CHECK_IN(target, F32);
   float* ll = nullptr;
   float* le = nullptr;
-  if (loss_last.has_value() && loss_last->defined()) { CHECK_IN((*loss_last), F32); ll = loss_last->data_ptr<float>(); }
-  if (loss_ema.has_value() && loss_ema->defined()) { CHECK_IN((*loss_ema), F32); le = loss_ema->data_ptr<float>(); }
+  if (given(loss_last)) { CHECK_IN((*loss_last), F32); ll = loss_last->data_ptr<float>(); }
+  if (given(loss_ema)) { CHECK_IN((*loss_ema), F32); le = loss_ema->data_ptr<float>(); }
   const c10::DeviceGuard guard(pred.device());
   TORCH_CHECK(pred.sizes() == target.sizes() && pred.dim() == 4, "pred/target shape");
   const int B = pred.size(0), C = pred.size(1), H = pred.size(2), W = pred.size(3);
@@ -563,22 +566,28 @@ Tensor img_to_tokgrad(Tensor dimg, int64_t N, int64_t patch) {
   return dtok;
 }
 
+// dx = dy w of linear_dgrad and linear_dgrad_gelu: dy [M][Nout], w [Nout][K] -> [M][K] (g.M x g.N)
+GemmArgs dgrad_args(const Tensor& dy, const Tensor& w) {
+  TORCH_CHECK(dy.dim() == 2 && w.dim() == 2 && dy.size(1) == w.size(0), "dgrad shapes");
+  const int M = dy.size(0), Nout = w.size(0), K = w.size(1);
+  TORCH_CHECK(Nout % 8 == 0 && K % 8 == 0, "dgrad dims must be multiples of 8");
+  GemmArgs g;
+  g.A = dy.data_ptr(); g.B = w.data_ptr();
+  g.M = M; g.N = K; g.K = Nout; g.lda = Nout; g.ldb = K; g.ldc = K;
+  return g;
+}
+
 // splits > 1 (fp32 only): [splits, M, K] partial products over K slices
 Tensor linear_dgrad(Tensor dy, Tensor w, bool out_fp32, int64_t splits) {
   CHECK_IN(dy, BF16); CHECK_IN(w, BF16);
   const c10::DeviceGuard guard(dy.device());
-  TORCH_CHECK(dy.dim() == 2 && w.dim() == 2 && dy.size(1) == w.size(0), "dgrad shapes");
-  const int M = dy.size(0), Nout = w.size(0), K = w.size(1);
-  TORCH_CHECK(Nout % 8 == 0 && K % 8 == 0, "dgrad dims must be multiples of 8");
+  GemmArgs g = dgrad_args(dy, w);
   TORCH_CHECK(splits >= 1 && splits <= 4, "dgrad K split: 1..4");
-  auto dx = splits > 1 ? at::empty({splits, M, K}, dy.options().dtype(out_fp32 ? F32 : BF16))
-                       : at::empty({M, K}, dy.options().dtype(out_fp32 ? F32 : BF16));
-  GemmArgs g;
-  g.A = dy.data_ptr(); g.B = w.data_ptr();
-  g.M = M; g.N = K; g.K = Nout; g.lda = Nout; g.ldb = K;
-  g.C = dx.data_ptr(); g.ldc = K;
+  auto dx = splits > 1 ? at::empty({splits, g.M, g.N}, dy.options().dtype(out_fp32 ? F32 : BF16))
+                       : at::empty({g.M, g.N}, dy.options().dtype(out_fp32 ? F32 : BF16));
+  g.C = dx.data_ptr();
   g.splits = (int)splits;
-  g.split_stride = (long long)M * K;
+  g.split_stride = (long long)g.M * g.N;
   gemm_dgrad(g, out_fp32 ? EPI_F32 : EPI_BF16, cur_stream());
   return dx;
 }
@@ -586,15 +595,10 @@ Tensor linear_dgrad(Tensor dy, Tensor w, bool out_fp32, int64_t splits) {
 Tensor linear_dgrad_gelu(Tensor dy, Tensor w, Tensor u, Tensor rng, int64_t site, double p) {
   CHECK_IN(dy, BF16); CHECK_IN(w, BF16); CHECK_IN(u, BF16); check_rng(rng);
   const c10::DeviceGuard guard(dy.device());
-  TORCH_CHECK(dy.dim() == 2 && w.dim() == 2 && dy.size(1) == w.size(0), "dgrad shapes");
-  const int M = dy.size(0), Nout = w.size(0), K = w.size(1);
-  TORCH_CHECK(u.numel() == (int64_t)M * K, "u shape");
-  TORCH_CHECK(Nout % 8 == 0 && K % 8 == 0, "dgrad dims must be multiples of 8");
-  auto du = at::empty({M, K}, dy.options());
-  GemmArgs g;
-  g.A = dy.data_ptr(); g.B = w.data_ptr();
-  g.M = M; g.N = K; g.K = Nout; g.lda = Nout; g.ldb = K;
-  g.C = du.data_ptr(); g.ldc = K; g.aux = u.data_ptr();
+  GemmArgs g = dgrad_args(dy, w);
+  TORCH_CHECK(u.numel() == (int64_t)g.M * g.N, "u shape");
+  auto du = at::empty({g.M, g.N}, dy.options());
+  g.C = du.data_ptr(); g.aux = u.data_ptr();
   g.rng = rng.data_ptr<int64_t>(); g.site_drop = site; g.p_drop = p;
   gemm_dgrad(g, EPI_DGELU, cur_stream());
   return du;
@@ -618,28 +622,36 @@ Tensor linear_dgrad_gelu_t(Tensor dy, Tensor wt, Tensor u, Tensor rng, int64_t s
   return du;
 }
 
-void linear_wgrad(Tensor dy, Tensor x, Tensor dw, c10::optional<Tensor> db) {
-  CHECK_IN(dy, BF16); CHECK_IN(x, BF16); CHECK_IN(dw, F32);
-  const c10::DeviceGuard guard(dy.device());
-  TORCH_CHECK(dy.dim() == 2 && x.dim() == 2 && dy.size(0) == x.size(0), "wgrad shapes");
+// dW (+)= dy^T x, db (+)= column sums of dy, of linear_wgrad and of every problem of
+// linear_wgrad_multi: dy [M][Nout], x [M][K], dw Nout*K fp32, db (optional) Nout fp32.
+// group: a problem of the multi launch, which also refuses empty operands.
+GemmArgs wgrad_args(const Tensor& dy, const Tensor& x, const Tensor& dw, const c10::optional<Tensor>& db, bool group) {
+  const char* who = group ? "wgrad_group" : "wgrad";
+  TORCH_CHECK(dy.dim() == 2 && x.dim() == 2 && dy.size(0) == x.size(0) && (!group || dy.size(0) > 0), who, " shapes");
   const int M = dy.size(0), Nout = dy.size(1), K = x.size(1);
-  TORCH_CHECK(dw.numel() == (int64_t)Nout * K, "dw shape");
-  TORCH_CHECK(Nout % 8 == 0 && K % 8 == 0, "wgrad dims must be multiples of 8");
-  float* dbp = nullptr;
-  if (db.has_value() && db->defined()) {
-    CHECK_IN((*db), F32);
-    TORCH_CHECK(db->numel() == Nout, "db shape");
-    dbp = db->data_ptr<float>();
-  }
+  TORCH_CHECK(dw.numel() == (int64_t)Nout * K, who, ": dw shape");
+  TORCH_CHECK((!group || (Nout > 0 && K > 0)) && Nout % 8 == 0 && K % 8 == 0, "wgrad dims must be multiples of 8");
   GemmArgs g;
   g.A = dy.data_ptr(); g.B = x.data_ptr();
   g.M = Nout; g.N = K; g.K = M; g.lda = Nout; g.ldb = K;
-  g.C = dw.data_ptr(); g.ldc = K; g.bias = dbp;
+  g.C = dw.data_ptr(); g.ldc = K;
+  if (given(db)) {
+    CHECK_IN((*db), F32);
+    TORCH_CHECK(db->numel() == Nout, who, ": db shape");
+    g.bias = db->data_ptr<float>();
+  }
+  return g;
+}
+
+void linear_wgrad(Tensor dy, Tensor x, Tensor dw, c10::optional<Tensor> db) {
+  CHECK_IN(dy, BF16); CHECK_IN(x, BF16); CHECK_IN(dw, F32);
+  const c10::DeviceGuard guard(dy.device());
+  const GemmArgs g = wgrad_args(dy, x, dw, db, false);
   // split the token reduction so the grid fills the chip; fp32 atomics combine the
   // slices, so keep the split count small (atomic bytes = splits x |dW|, chip-wide
   // atomic rate ~1.3 TB/s)
-  const int tiles = ((Nout + 63) / 64) * ((K + 63) / 64);
-  const int kt = (M + 63) / 64;
+  const int tiles = ((g.M + 63) / 64) * ((g.N + 63) / 64);
+  const int kt = (g.K + 63) / 64;
   constexpr int max_splits = 8;
   int splits = (256 + tiles - 1) / tiles;
   if (splits > max_splits) splits = max_splits;
@@ -668,20 +680,7 @@ static std::vector<GemmArgs> wgrad_probs(const std::vector<Tensor>& dys, const s
     CHECK_IN(dy, BF16); CHECK_IN(x, BF16); CHECK_IN(dw, F32);
     TORCH_CHECK(dy.device() == dys[0].device() && x.device() == dy.device() && dw.device() == dy.device(),
                 "wgrad_group: tensors on different devices");
-    TORCH_CHECK(dy.dim() == 2 && x.dim() == 2 && dy.size(0) == x.size(0) && dy.size(0) > 0, "wgrad_group shapes");
-    const int M = dy.size(0), Nout = dy.size(1), K = x.size(1);
-    TORCH_CHECK(dw.numel() == (int64_t)Nout * K, "wgrad_group: dw shape");
-    TORCH_CHECK(Nout > 0 && K > 0 && Nout % 8 == 0 && K % 8 == 0, "wgrad dims must be multiples of 8");
-    GemmArgs g;
-    g.A = dy.data_ptr(); g.B = x.data_ptr();
-    g.M = Nout; g.N = K; g.K = M; g.lda = Nout; g.ldb = K;
-    g.C = dw.data_ptr(); g.ldc = K;
-    if (dbs[i].has_value() && dbs[i]->defined()) {
-      CHECK_IN((*dbs[i]), F32);
-      TORCH_CHECK(dbs[i]->numel() == Nout, "wgrad_group: db shape");
-      g.bias = dbs[i]->data_ptr<float>();
-    }
-    probs.push_back(g);
+    probs.push_back(wgrad_args(dy, x, dw, dbs[i], true));
   }
   return probs;
 }
@@ -716,9 +715,9 @@ void linear_wgrad_multi(std::vector<Tensor> dys, std::vector<Tensor> xs, std::ve
   // ---- validate
   const std::vector<GemmArgs> probs = wgrad_probs(dys, xs, dws, dbs);
   const c10::DeviceGuard guard(dys[0].device());
-  const bool fused = sq_parts.has_value() && sq_parts->defined();
+  const bool fused = given(sq_parts);
   // embedding gradients + LayerNorm finalize as extra workgroups (embed_parts.h)
-  const bool with_emb = emb_g.has_value() && emb_g->defined();
+  const bool with_emb = given(emb_g);
   WgradEmbed we{};
   if (with_emb) {
     const Tensor& g = *emb_g;
@@ -733,7 +732,7 @@ void linear_wgrad_multi(std::vector<Tensor> dys, std::vector<Tensor> xs, std::ve
                            emb_pos->data_ptr<float>(), emb_temb->data_ptr<float>(), B, N, D,
                            emb_rng->data_ptr<int64_t>(), (int)emb_site, emb_p, 0, B);
     we.e.owners = (int)emb_owners;
-    if (ln_ws.has_value() && ln_ws->defined()) {
+    if (given(ln_ws)) {
       CHECK_IN((*ln_ws), F32); CHECK_IN((*ln_ptrs), I64);
       we.rf.G = ln_ptrs->numel();
       we.rf.C = (int)ln_C;
@@ -747,7 +746,7 @@ void linear_wgrad_multi(std::vector<Tensor> dys, std::vector<Tensor> xs, std::ve
       we.rf.store = ln_store ? 1 : 0;
     }
   }
-  const bool have_tickets = split_tickets.has_value() && split_tickets->defined();
+  const bool have_tickets = given(split_tickets);
   if (have_tickets) {
     CHECK_IN((*split_tickets), at::kInt);
     TORCH_CHECK(split_tickets->numel() >= WGRAD_TICKETS && split_tickets->device() == dys[0].device(),
@@ -759,7 +758,7 @@ void linear_wgrad_multi(std::vector<Tensor> dys, std::vector<Tensor> xs, std::ve
   WgradRanges targets, skipped;
   int np = 0;
   if (fused) {
-    TORCH_CHECK(arena.has_value() && arena->defined(), "wgrad_multi: grad-norm partials need the gradient arena");
+    TORCH_CHECK(given(arena), "wgrad_multi: grad-norm partials need the gradient arena");
     CHECK_IN((*sq_parts), F32); CHECK_IN((*arena), F32);
     np = check_parts(*sq_parts, "wgrad_multi");
     const float* base = arena->data_ptr<float>();
@@ -770,7 +769,7 @@ void linear_wgrad_multi(std::vector<Tensor> dys, std::vector<Tensor> xs, std::ve
     };
     for (size_t i = 0; i < dws.size(); ++i) {
       add(targets, dws[i]);
-      if (dbs[i].has_value() && dbs[i]->defined()) add(targets, *dbs[i]);
+      if (given(dbs[i])) add(targets, *dbs[i]);
     }
     if (lz_hi > lz_lo) skipped.emplace_back(lz_lo, lz_hi);
     if (with_emb) {
@@ -903,14 +902,14 @@ std::tuple<Tensor, Tensor> layernorm_bwd(Tensor dy, Tensor x, Tensor mean, Tenso
                   gamma.numel() == D && dgamma.numel() == D && dbeta.numel() == D && M % N == 0 && parts <= 4,
               "layernorm_bwd shapes");
   const float* gr = nullptr;
-  if (g_res.has_value() && g_res->defined()) {
+  if (given(g_res)) {
     CHECK_IN((*g_res), F32);
     TORCH_CHECK(g_res->numel() == x.numel(), "g_res shape");
     gr = g_res->data_ptr<float>();
   }
   // workspace [S][2D]: one dgamma||dbeta slot per backward workgroup (overwritten)
   const int S = ln_bwd_workgroups(M);
-  const bool own_ws = !(ws.has_value() && ws->defined());
+  const bool own_ws = !given(ws);
   const auto f32o = x.options().dtype(F32);
   Tensor w = own_ws ? at::empty({S, 2 * D}, f32o) : *ws;
   if (!own_ws) {
@@ -919,7 +918,7 @@ std::tuple<Tensor, Tensor> layernorm_bwd(Tensor dy, Tensor x, Tensor mean, Tenso
                 " rows for M = ", M, ")");
   }
   void* gpp = nullptr;
-  if (gp_out.has_value() && gp_out->defined()) {  // the patch-embedding input gradient
+  if (given(gp_out)) {  // the patch-embedding input gradient
     CHECK_IN((*gp_out), BF16);
     TORCH_CHECK(N > 1 && gp_out->numel() == (int64_t)(M / N) * (N - 1) * D, "gp_out must be [B*(N-1), D]");
     gpp = gp_out->data_ptr();
@@ -928,8 +927,8 @@ std::tuple<Tensor, Tensor> layernorm_bwd(Tensor dy, Tensor x, Tensor mean, Tenso
   // gradient of the GEMM that consumed it through the LayerNorm fold
   const float* bp = nullptr;
   void* yp = nullptr;
-  if (y_out.has_value() && y_out->defined()) {
-    TORCH_CHECK(beta.has_value() && beta->defined(), "y_out needs beta");
+  if (given(y_out)) {
+    TORCH_CHECK(given(beta), "y_out needs beta");
     CHECK_IN((*beta), F32); CHECK_IN((*y_out), BF16);
     TORCH_CHECK(beta->numel() == D && y_out->numel() == x.numel(), "beta / y_out shapes");
     bp = beta->data_ptr<float>();
@@ -1016,9 +1015,9 @@ Tensor embed_bwd(Tensor g, Tensor t, Tensor rng, int64_t site, double p, Tensor 
               "embed_bwd shapes");
   auto gpatch = at::empty({(int64_t)B * (N - 1), D}, g.options().dtype(BF16));
   ReplicaFinal rf;
-  if (ln_ws.has_value() && ln_ws->defined()) {  // replica_reduce_ folded into this launch
+  if (given(ln_ws)) {  // replica_reduce_ folded into this launch
     CHECK_IN((*ln_ws), F32);
-    TORCH_CHECK(ln_ptrs.has_value() && ln_ptrs->defined(), "ln_ws needs ln_ptrs");
+    TORCH_CHECK(given(ln_ptrs), "ln_ws needs ln_ptrs");
     CHECK_IN((*ln_ptrs), I64);
     rf.G = ln_ptrs->numel();
     rf.C = ln_C;
@@ -1054,18 +1053,18 @@ void adamw_step(Tensor p, Tensor g, Tensor m, Tensor v, c10::optional<Tensor> pb
               "adamw shapes");
   const int np = check_parts(sq, "adamw");
   void* pb = nullptr;
-  if (pbf.has_value() && pbf->defined()) {
+  if (given(pbf)) {
     CHECK_IN((*pbf), BF16);
     TORCH_CHECK(pbf->numel() == n, "bf16 shadow size");
     pb = pbf->data_ptr();
   }
   float* ld = nullptr;
-  if (lazy_decay.has_value() && lazy_decay->defined() && lz_hi > lz_lo) {
+  if (given(lazy_decay) && lz_hi > lz_lo) {
     CHECK_IN((*lazy_decay), F32);
     ld = lazy_decay->data_ptr<float>();
   }
   float* ep = nullptr;
-  if (ema.has_value() && ema->defined()) {
+  if (given(ema)) {
     CHECK_IN((*ema), F32);
     TORCH_CHECK(ema->numel() == n, "weight EMA arena size");
     TORCH_CHECK(ema_decay >= 0.0 && ema_decay < 1.0, "ema_decay must be in [0, 1), got ", ema_decay);
@@ -1082,7 +1081,7 @@ void advance_counters(Tensor step, Tensor rng, c10::optional<Tensor> sq) {
   const c10::DeviceGuard guard(step.device());
   const float* s = nullptr;
   int np = 0;
-  if (sq.has_value() && sq->defined()) {
+  if (given(sq)) {
     CHECK_IN((*sq), F32);
     np = check_parts(*sq, "advance");
     s = sq->data_ptr<float>();
@@ -1124,7 +1123,7 @@ static void cold_step_impl(Tensor& x, const Tensor& x0, const Tensor& t, int64_t
   const char *xp = (const char*)x.data_ptr(), *sp = (const char*)x0.data_ptr();
   TORCH_CHECK(xp + n * 4 <= sp || sp + n * 4 <= xp, "cold_step: x and x0 must not alias");
   TORCH_CHECK((uintptr_t)xp % 16 == 0, "cold_step: x must be 16-byte aligned");
-  const bool have_out = patches_out.has_value() && patches_out->defined();
+  const bool have_out = given(patches_out);
   if (rows || have_out) {
     TORCH_CHECK(patch >= 1 && H % patch == 0 && W % patch == 0, "cold_step: image size must be divisible by patch");
     TORCH_CHECK((C * patch * patch) % 4 == 0, "cold_step: C*p*p must be a multiple of 4");
@@ -1178,7 +1177,7 @@ void repaint_rows_(Tensor x, Tensor known, Tensor mask, Tensor coef, Tensor rng,
   TORCH_CHECK((uintptr_t)xp % 16 == 0 && (uintptr_t)kp % 16 == 0, "repaint_rows_: x and known must be 16-byte aligned");
   TORCH_CHECK((uintptr_t)mask.data_ptr() % 4 == 0, "repaint_rows_: mask must be 4-byte aligned");
   void* po = nullptr;
-  if (patches_out.has_value() && patches_out->defined()) {
+  if (given(patches_out)) {
     CHECK_IN((*patches_out), BF16);
     TORCH_CHECK(patches_out->device() == x.device() && patches_out->sizes() == x.sizes(),
                 "repaint_rows_: patches_out must be on x's device and of its shape");
@@ -1212,7 +1211,7 @@ std::tuple<Tensor, Tensor> pixelate_pair(Tensor img, c10::optional<Tensor> idx, 
   const c10::DeviceGuard guard(img.device());
   TORCH_CHECK(img.dim() == 4 && t.numel() == B, "pixelate shapes");
   const int64_t* ip = nullptr;
-  if (idx.has_value() && idx->defined()) {
+  if (given(idx)) {
     CHECK_IN((*idx), I64);
     TORCH_CHECK(idx->numel() == B, "idx shape");
     ip = idx->data_ptr<int64_t>();
@@ -1281,7 +1280,7 @@ void ln_fold_(std::vector<Tensor> ws, std::vector<Tensor> gammas, std::vector<Te
     FoldJob& j = tb.j[i];
     j.w = ws[i].data_ptr(); j.gamma = gammas[i].data_ptr<float>(); j.beta = betas[i].data_ptr<float>();
     j.bias = nullptr;
-    if (biases[i].has_value() && biases[i]->defined()) {
+    if (given(biases[i])) {
       CHECK_IN((*biases[i]), F32);
       TORCH_CHECK(biases[i]->numel() == R, "ln_fold_: bias shape");
       j.bias = biases[i]->data_ptr<float>();
@@ -1291,17 +1290,17 @@ void ln_fold_(std::vector<Tensor> ws, std::vector<Tensor> gammas, std::vector<Te
     rows += R;
   }
   tb.start[n] = rows;
-  if (step.has_value() && step->defined()) {  // training-step tail in the same launch
+  if (given(step)) {  // training-step tail in the same launch
     CHECK_IN((*step), I64); check_rng(*rng);
-    TORCH_CHECK(loss_parts.has_value() && loss_parts->defined() && sq.has_value() && sq->defined(),
+    TORCH_CHECK(given(loss_parts) && given(sq),
                 "step tail needs loss_parts and sq");
     CHECK_IN((*loss_parts), F32); CHECK_IN((*sq), F32);
     tb.sq_n = check_parts(*sq, "ln_fold_ tail");
     tb.tail = 1;
     tb.loss_parts = loss_parts->data_ptr<float>();
     tb.loss_nparts = (int)loss_parts->numel();
-    if (loss_last.has_value() && loss_last->defined()) { CHECK_IN((*loss_last), F32); tb.loss_last = loss_last->data_ptr<float>(); }
-    if (loss_ema.has_value() && loss_ema->defined()) { CHECK_IN((*loss_ema), F32); tb.loss_ema = loss_ema->data_ptr<float>(); }
+    if (given(loss_last)) { CHECK_IN((*loss_last), F32); tb.loss_last = loss_last->data_ptr<float>(); }
+    if (given(loss_ema)) { CHECK_IN((*loss_ema), F32); tb.loss_ema = loss_ema->data_ptr<float>(); }
     tb.ema_decay = (float)ema_decay;
     tb.step = step->data_ptr<int64_t>();
     tb.rng = rng->data_ptr<int64_t>();

@@ -266,7 +266,7 @@ __device__ __forceinline__ void gemm_dma_body(const GemmParams& p, int tm, int t
   // consecutive output columns of one row in each lane, no quad transpose.
   constexpr bool VEC = UsesVecEpi<EPI>::value;
   VecEpi<EPI, FM, FN, VEC> ep;
-  if (VEC) ep.prefetch(p, m0 + wm * TM, n0 + wn * TN, g, li);
+  if constexpr (VEC) ep.prefetch(p, m0 + wm * TM, n0 + wn * TN, g, li);
 
   // main loop; the bias-gradient MFMA variant is a separate instantiation so the
   // loop carries no per-k-step branch (one made hipcc shuffle the accumulators
@@ -382,7 +382,7 @@ __device__ __forceinline__ void gemm_dma_body(const GemmParams& p, int tm, int t
       }
   }
 
-  if (VEC) ep.finish(p, acc, li);
+  if constexpr (VEC) ep.finish(p, acc, li);
   else run_epilogue_scalar<EPI, FM, FN>(p, acc, m0 + wm * TM, n0 + wn * TN, g, li);
 #ifdef DDIM_COLD_GEMM_STAMPS
   if (p.stamps) {
@@ -779,7 +779,7 @@ static void check_vec(const GemmParams& p, int epi) {
 void gemm_nt(const GemmArgs& a, int epi, hipStream_t stream) {
   GemmParams p = gemm_params_from_args(a);
   check_vec(p, epi);
-  if (epi == EPI_HEADRS && ((p.head_mode != 5 && p.head_mode != 6) || p.rng == nullptr || p.coef == nullptr ||
+  if (epi == EPI_HEADRS && ((p.head_mode != HEAD_ETA && p.head_mode != HEAD_ETA_EACH) || p.rng == nullptr || p.coef == nullptr ||
                             p.res == nullptr || p.C2 == nullptr))
     throw std::runtime_error("gemm_nt: EPI_HEADRS needs head mode 5 or 6 with rng, coef, x_t and x0_out");
   launch_auto(false, false, epi, p, 1, stream);

@@ -36,19 +36,19 @@ struct GemmParams {
   const int64_t* tsteps;
   int emb_dim;
   int ktiles_per_split;
-  const float* coef;     // HEAD mode 1: {sqrt a_t, sqrt(1-a_t), sqrt a_tk, sqrt(1-a_tk)} (device);
-                         //   mode 4: one such row per sample ([batch][4])
+  const float* coef;     // HEAD_DDIM: {sqrt a_t, sqrt(1-a_t), sqrt a_tk, sqrt(1-a_tk)} (device);
+                         //   HEAD_DDIM_EACH: one such row per sample ([batch][4])
   long long split_stride;  // EPI_F32: elements between the K-split output slices
-  int head_mode;         // HEAD: 0 image, 1 fused DDIM step (res = x_t in, C = x_next, C2 = x0), 2 clamp,
-                         //   3 training loss (res = target image, C2 = token-layout grad, loss_parts),
-                         //   4 DDIM step with per-sample coefficients (img2img: a sample that has
-                         //     not reached its start step has the row {0, 1, 0, 1}: x_next = x_t)
-                         // HEADRS: 5 stochastic DDIM step, coef = one row of 8 floats {c0, c1, c2, dir,
-                         //   sigma, 0, 0, 0}; 6 one such row per sample ([batch][8]; not started:
-                         //   {0, 1, 0, 1, 0, ..}).  rng = {seed, 0}, site_drop = the step's noise site
-  float loss_beta;       // HEAD mode 3: smooth-L1 beta and 1/numel
+  int head_mode;         // a HeadMode (kernels.h).  HEAD / HEADR: HEAD_IMAGE, HEAD_DDIM (res = x_t in,
+                         //   C = x_next, C2 = x0), HEAD_CLAMP, HEAD_LOSS (res = target image, C2 =
+                         //   token-layout grad, loss_parts), HEAD_DDIM_EACH (img2img: a sample that has
+                         //   not reached its start step has the row {0, 1, 0, 1}: x_next = x_t).
+                         // HEADRS: HEAD_ETA, the stochastic DDIM step, coef = one row of 8 floats {c0,
+                         //   c1, c2, dir, sigma, 0, 0, 0}; HEAD_ETA_EACH, one such row per sample ([batch][8];
+                         //   not started: {0, 1, 0, 1, 0, ..}).  rng = {seed, 0}, site_drop = the step's noise site
+  float loss_beta;       // HEAD_LOSS: smooth-L1 beta and 1/numel
   float loss_inv_n;
-  float* loss_parts;     // HEAD mode 3: one loss partial per workgroup (gridDim.x entries)
+  float* loss_parts;     // HEAD_LOSS: one loss partial per workgroup (gridDim.x entries)
   // LayerNorm fold (GemmArgs): consumer side
   const float* ln_st;
   const float* ln_c;
@@ -58,7 +58,7 @@ struct GemmParams {
   // producer side
   float* st_out;
   bf16* xb_out;
-  // sampler steps: HEAD modes 1/2 also store the new image in the patch-row layout
+  // sampler steps: the DDIM and clamp head modes also store the new image in the patch-row layout
   // (bf16 [B*P][C*p*p], the next step's patch-embedding A operand: no patchify
   // launch); EMBED with cls_src also writes the cls rows (cls + pos[0] + temb[t])
   bf16* patch_out;
@@ -86,54 +86,27 @@ static __device__ const int64_t kEpiNoRng[2] = {0, 0};  // rng words of GEMMs wi
 __device__ __forceinline__ uint32_t stamp_now() { return (uint32_t)__builtin_amdgcn_s_memrealtime(); }
 
 
-// Epilogue in two phases: (1) every global load the epilogue needs (bias per
-// column, residual / saved pre-activation / pos+time embedding per element) is
-// issued for the whole fragment tile, (2) compute + store.  Interleaving them
-// per element serialises the tile on memory latency (the loads may alias the
-// stores through GemmParams, so the compiler cannot hoist them).
-// The epilogue is "load everything, then compute + store": interleaving per-element
-// loads (bias / residual / saved pre-activation / embeddings, which may alias the
-// stores through GemmParams) with stores serialises the tile on memory latency.
+// Every epilogue is "load everything, then compute + store": all the global loads it needs
+// (bias per column, residual / saved pre-activation / pos+time embedding per element) are
+// issued for the whole fragment tile first.  Interleaving them per element with the stores
+// serialises the tile on memory latency (the loads may alias the stores through GemmParams,
+// so the compiler cannot hoist them).
 // Every output index is separable, idx = rowoff(m) + coloff(n), so the integer
 // divisions (token -> sample, column -> head / pixel) are done once per row and
 // once per column of the lane's fragment, not per element.
-struct RowInfo {
-  long long off;  // row part of the destination index (-1: skip row)
-  int b;          // sample index (drop-path) / helper
-};
 
+// Which of the two epilogue implementations an epilogue takes: VecEpi (4 consecutive
+// columns per lane) for all but
+//   HEAD: its output columns are pixels of an image, not contiguous in memory;
+//   ATOMIC: in the accumulator layout one atomic instruction covers 4 rows x 64 B; after
+//     the quad transpose it would touch 16 rows (4x the cache lines per instruction) -
+//     measured 10% slower per step,
+// which take run_epilogue_scalar.  A compile-time choice: neither implementation is
+// instantiated for the other's epilogues.
 template <int EPI>
-__device__ __forceinline__ RowInfo epi_row(const GemmParams& p, int m) {
-  RowInfo ri;
-  ri.b = 0;
-  if (EPI == EPI_QKV) {
-    const int b = m / p.tokens, tok = m - b * p.tokens;
-    ri.off = ((long long)b * p.heads * p.tokens + tok) * p.hd;
-  } else if (EPI == EPI_RESID) {
-    ri.off = (long long)m * p.N;
-    ri.b = m / p.tokens;
-  } else if (EPI == EPI_GELU || EPI == EPI_DGELU) {
-    ri.off = (long long)m * p.N;
-  } else if (EPI == EPI_HEAD) {
-    const int b = m / p.tokens, tok = m - b * p.tokens;
-    ri.b = b;  // sample (head mode 4: per-sample DDIM coefficients)
-    if (tok == 0) {
-      ri.off = -1;
-    } else {
-      const int P = p.patch, Wp = p.img_w / P;
-      const int patch = tok - 1, hp = patch / Wp, wp = patch - hp * Wp;
-      ri.off = (long long)b * p.chans * p.img_h * p.img_w + (long long)hp * P * p.img_w + wp * P;
-    }
-  } else if (EPI == EPI_EMBED) {
-    const int Pn = p.tokens;
-    const int b = m / Pn, patch = m - b * Pn;
-    ri.off = ((long long)b * (Pn + 1) + patch + 1) * p.emb_dim;
-    ri.b = b;
-  } else {
-    ri.off = (long long)m * p.ldc;
-  }
-  return ri;
-}
+struct UsesVecEpi {
+  static constexpr bool value = EPI != EPI_HEAD && EPI != EPI_ATOMIC;
+};
 
 template <int EPI>
 __device__ __forceinline__ long long epi_col(const GemmParams& p, int n) {
@@ -212,13 +185,9 @@ __device__ __forceinline__ RowInfo32 epi_row32(const GemmParams& p, int m) {
     const int b = divmagic(m, p.tokens, p.tok_magic);
     ri.off = m * p.N;
     ri.b = m - b * p.tokens == 0 ? -1 : b;
-  } else if (EPI == EPI_HEADR) {
-    // token row m of sample b -> patch row b*P + tok - 1 = m - b - 1 (cls rows skipped)
-    const int b = divmagic(m, p.tokens, p.tok_magic), tok = m - b * p.tokens;
-    ri.off = tok == 0 ? -1 : (m - b - 1) * p.N;
-    ri.b = b;
-  } else if (EPI == EPI_HEADRS) {
-    // as HEADR; off + column is also the element's index in the step's noise draw
+  } else if (EPI == EPI_HEADR || EPI == EPI_HEADRS) {
+    // token row m of sample b -> patch row b*P + tok - 1 = m - b - 1 (cls rows skipped);
+    // HEADRS: off + column is also the element's index in the step's noise draw
     const int b = divmagic(m, p.tokens, p.tok_magic), tok = m - b * p.tokens;
     ri.off = tok == 0 ? -1 : (m - b - 1) * p.N;
     ri.b = b;
@@ -248,80 +217,84 @@ __device__ __forceinline__ int fold_token_row(const GemmParams& p, int m) {
   return m;
 }
 
-// returns the stored fp32 value of the residual / embedding epilogues (LayerNorm statistics)
+// ---- Scalar whole-tile epilogue of the two epilogues outside VecEpi (UsesVecEpi): one
+// 4-byte element per lane and register, acc[FM][FN] fragment tiles at
+// (mb + i*16 + 4g + r, nb + j*16 + li).
+//   EPI_HEAD, the image-layout head (HEAD_IMAGE .. HEAD_DDIM_EACH): LayerNorm fold
+//     consumer, + bias, then per mode the image store, the training loss with its
+//     token-layout gradient, the clamp, or the DDIM update (one coefficient row, or one
+//     per sample); the sampler modes also write the new image as bf16 patch rows;
+//   EPI_ATOMIC: C += acc in fp32 atomics (split weight gradient; no bias, no fold).
+// 64-bit destination index, row part + column part (epi_col).
+struct RowInfo {
+  long long off;  // row part of the destination index (-1: skip row)
+  int b;          // HEAD: sample (HEAD_DDIM_EACH: its coefficient row)
+};
+
 template <int EPI>
-__device__ __forceinline__ float epilogue(const GemmParams& p, long long idx, int rb, float v, float pre,
-                                          uint32_t salt_drop, uint32_t salt_dp, const f32x4& cf) {
-  if (EPI == EPI_BF16) {
-    reinterpret_cast<bf16*>(p.C)[idx + blockIdx.z * p.split_stride] = f2bf(v);
-  } else if (EPI == EPI_F32) {
-    reinterpret_cast<float*>(p.C)[idx + blockIdx.z * p.split_stride] = v;
-  } else if (EPI == EPI_ATOMIC) {
-    atomicAdd(reinterpret_cast<float*>(p.C) + idx, v);
-  } else if (EPI == EPI_ACC) {
-    reinterpret_cast<float*>(p.C)[idx] = pre + v;  // pre = old C (loaded in phase 1)
-  } else if (EPI == EPI_QKV) {
-    reinterpret_cast<bf16*>(p.C)[idx] = f2bf(v);
-  } else if (EPI == EPI_RESID) {
-    if (p.thr_drop) v = dropout_keep(salt_drop, (uint32_t)idx, p.thr_drop) ? v * p.scale_drop : 0.f;
-    if (p.thr_dp) v = dropout_keep(salt_dp, (uint32_t)rb, p.thr_dp) ? v * p.scale_dp : 0.f;
-    reinterpret_cast<float*>(p.C)[idx] = pre + v;
-    return pre + v;
-  } else if (EPI == EPI_GELU) {
-    reinterpret_cast<bf16*>(p.C)[idx] = f2bf(v);
-    float h = gelu_f(v);
-    if (p.thr_drop) h = dropout_keep(salt_drop, (uint32_t)idx, p.thr_drop) ? h * p.scale_drop : 0.f;
-    reinterpret_cast<bf16*>(p.C2)[idx] = f2bf(h);
-  } else if (EPI == EPI_DGELU) {
-    if (p.thr_drop) v = dropout_keep(salt_drop, (uint32_t)idx, p.thr_drop) ? v * p.scale_drop : 0.f;
-    reinterpret_cast<bf16*>(p.C)[idx] = f2bf(v * gelu_grad_f(pre));
-  } else if (EPI == EPI_HEAD) {
-    if (p.head_mode == 0) {
-      reinterpret_cast<float*>(p.C)[idx] = v;
-    } else if (p.head_mode == 3) {
-      // smooth-L1 vs the target pixel (`pre`), multi_gpu_trainer.py:124: the image
-      // is never written; returns the element's loss / numel (the gradient is
-      // stored by the caller in the token layout)
-      const float d = v - pre, ad = fabsf(d), b = p.loss_beta;
-      return (ad < b ? 0.5f * d * d / b : ad - 0.5f * b) * p.loss_inv_n;
+__device__ __forceinline__ RowInfo epi_row(const GemmParams& p, int m) {
+  RowInfo ri;
+  ri.b = 0;
+  if (EPI == EPI_HEAD) {
+    const int b = m / p.tokens, tok = m - b * p.tokens;
+    ri.b = b;
+    if (tok == 0) {
+      ri.off = -1;
     } else {
-      // the sampler's x0-hat clamp (ViT.py:229, ViT_draft2drawing.py:280), and for
-      // modes 1 / 4 the whole DDIM update (ViT.py:230-234) with x_t preloaded in `pre`
-      const float x0 = fminf(fmaxf(v, -1.f), 1.f);
-      if (p.head_mode == 2) {
-        reinterpret_cast<float*>(p.C)[idx] = x0;
-        return x0;
-      } else {
-        const float eps = (pre - cf[0] * x0) / cf[1];
-        const float xn = cf[2] * x0 + cf[3] * eps;
-        reinterpret_cast<float*>(p.C)[idx] = xn;
-        reinterpret_cast<float*>(p.C2)[idx] = x0;
-        return xn;
-      }
+      const int P = p.patch, Wp = p.img_w / P;
+      const int patch = tok - 1, hp = patch / Wp, wp = patch - hp * Wp;
+      ri.off = (long long)b * p.chans * p.img_h * p.img_w + (long long)hp * P * p.img_w + wp * P;
     }
-  } else if (EPI == EPI_EMBED) {
-    v += pre;
-    if (p.thr_drop) v = dropout_keep(salt_drop, (uint32_t)idx, p.thr_drop) ? v * p.scale_drop : 0.f;
+  } else {
+    ri.off = (long long)m * p.ldc;
+  }
+  return ri;
+}
+
+// one element: v = the GEMM's value (+ bias), pre = x_t / the target pixel (HEAD_DDIM*,
+// HEAD_LOSS), cf = the row's DDIM coefficients.  Returns the element's loss / numel
+// (HEAD_LOSS) or the new pixel (sampler modes).
+template <int EPI>
+__device__ __forceinline__ float epilogue(const GemmParams& p, long long idx, float v, float pre, const f32x4& cf) {
+  if (EPI == EPI_ATOMIC) {
+    atomicAdd(reinterpret_cast<float*>(p.C) + idx, v);
+  } else if (p.head_mode == HEAD_IMAGE) {
     reinterpret_cast<float*>(p.C)[idx] = v;
-    return v;
+  } else if (p.head_mode == HEAD_LOSS) {
+    // smooth-L1 vs the target pixel, multi_gpu_trainer.py:124: the image is never
+    // written (the gradient is stored by the caller in the token layout)
+    const float d = v - pre, ad = fabsf(d), b = p.loss_beta;
+    return (ad < b ? 0.5f * d * d / b : ad - 0.5f * b) * p.loss_inv_n;
+  } else {
+    // the sampler's x0-hat clamp (ViT.py:229, ViT_draft2drawing.py:280), and for the DDIM
+    // modes the whole update (ViT.py:230-234)
+    const float x0 = fminf(fmaxf(v, -1.f), 1.f);
+    if (p.head_mode == HEAD_CLAMP) {
+      reinterpret_cast<float*>(p.C)[idx] = x0;
+      return x0;
+    }
+    const float eps = (pre - cf[0] * x0) / cf[1];
+    const float xn = cf[2] * x0 + cf[3] * eps;
+    reinterpret_cast<float*>(p.C)[idx] = xn;
+    reinterpret_cast<float*>(p.C2)[idx] = x0;
+    return xn;
   }
   return 0.f;
 }
 
-// scalar whole-tile epilogue (HEAD: output columns are not contiguous in memory):
-// acc[FM][FN] fragment tiles at (mb + i*16 + 4g + r, nb + j*16 + li)
 template <int EPI, int FM, int FN>
 __device__ __forceinline__ void run_epilogue_scalar(const GemmParams& p, const f32x4 (&acc)[FM][FN], int mb, int nb,
                                              int g, int li) {
-  constexpr bool ELEM = EPI == EPI_RESID || EPI == EPI_DGELU || EPI == EPI_EMBED || EPI == EPI_ACC;
-  const bool head_ps = EPI == EPI_HEAD && p.head_mode == 4;  // per-sample coefficient rows
-  const bool head_ddim = EPI == EPI_HEAD && (p.head_mode == 1 || head_ps);
-  const bool head_loss = EPI == EPI_HEAD && p.head_mode == 3;
+  static_assert(EPI == EPI_HEAD || EPI == EPI_ATOMIC, "the scalar epilogue serves EPI_HEAD and EPI_ATOMIC only");
+  constexpr bool HEAD = EPI == EPI_HEAD;
+  const bool head_ps = HEAD && p.head_mode == HEAD_DDIM_EACH;  // per-sample coefficient rows
+  const bool head_ddim = HEAD && (p.head_mode == HEAD_DDIM || head_ps);
+  const bool head_loss = HEAD && p.head_mode == HEAD_LOSS;
   RowInfo rows[FM][4];
   long long cols[FN];
   bool colok[FN];
   float colb[FN];
-  const bool has_bias = (EPI != EPI_ATOMIC) && (EPI != EPI_ACC) && p.bias != nullptr;
+  const bool has_bias = HEAD && p.bias != nullptr;  // ATOMIC: bias is the bias-gradient target
 #pragma unroll
   for (int j = 0; j < FN; ++j) {
     const int n = nb + j * 16 + li;
@@ -338,8 +311,7 @@ __device__ __forceinline__ void run_epilogue_scalar(const GemmParams& p, const f
       if (m >= p.M) rows[i][r].off = -1;
     }
   // LayerNorm fold, consumer side: per-row statistics and per-column c
-  constexpr bool FC = FoldEpi<EPI>::CONSUMER, FP = FoldEpi<EPI>::PRODUCER;
-  const bool fold = FC && p.ln_st != nullptr;
+  const bool fold = FoldEpi<EPI>::CONSUMER && p.ln_st != nullptr;
   // slot li of each of the lane's rows (the 16 lanes of a row group hold all <= 16 slots)
   const int np_in = p.K / LN_SLOT;
   float2 lnst[FM][4];
@@ -355,7 +327,7 @@ __device__ __forceinline__ void run_epilogue_scalar(const GemmParams& p, const f
                        ? *reinterpret_cast<const float2*>(p.ln_st + 2 * ((size_t)m * np_in + li))
                        : make_float2(0.f, 0.f);
     }
-  // phase 1: element loads
+  // phase 1: element loads (x_t / the target pixel)
   float pre[FM][FN][4];
 #pragma unroll
   for (int i = 0; i < FM; ++i)
@@ -365,23 +337,9 @@ __device__ __forceinline__ void run_epilogue_scalar(const GemmParams& p, const f
       for (int r = 0; r < 4; ++r) {
         float v = 0.f;
         if ((head_ddim || head_loss) && rows[i][r].off >= 0 && colok[j]) v = p.res[rows[i][r].off + cols[j]];
-        if (ELEM && rows[i][r].off >= 0 && colok[j]) {
-          const int n = nb + j * 16 + li;
-          if (EPI == EPI_RESID) v = p.res[rows[i][r].off + n];
-          if (EPI == EPI_ACC && !p.acc_store) v = reinterpret_cast<const float*>(p.C)[rows[i][r].off + n];
-          if (EPI == EPI_DGELU) v = bf2f(p.aux[rows[i][r].off + n]);
-          if (EPI == EPI_EMBED) {
-            const int m = mb + i * 16 + 4 * g + r;
-            const int patch = m - rows[i][r].b * p.tokens;
-            v = p.pos[(size_t)(patch + 1) * p.emb_dim + n] + p.temb[(size_t)p.tsteps[rows[i][r].b] * p.emb_dim + n];
-          }
-        }
         pre[i][j][r] = v;
       }
   // phase 2: compute + store
-  uint32_t salt_drop = 0, salt_dp = 0;
-  if (p.thr_drop) salt_drop = site_salt(p.rng, p.site_drop);
-  if (p.thr_dp) salt_dp = site_salt(p.rng, p.site_dp);
   f32x4 cf = f32x4{0.f, 1.f, 0.f, 0.f};
   if (head_ddim && !head_ps) cf = f32x4{p.coef[0], p.coef[1], p.coef[2], p.coef[3]};
   float2 ms[FM][4];
@@ -405,15 +363,7 @@ __device__ __forceinline__ void run_epilogue_scalar(const GemmParams& p, const f
         p.ln_rstd[m] = ms[i][r].y;
       }
     }
-  const bool prod = FP && p.st_out != nullptr;
-  float lsum = 0.f;  // HEAD mode 3: this lane's loss contributions
-  float2 part[FM][4][(FN + 1) / 2];  // producer (debug path): per-slot partials of the lane's rows
-#pragma unroll
-  for (int i = 0; i < FM; ++i)
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-      for (int sl = 0; sl < (FN + 1) / 2; ++sl) part[i][r][sl] = make_float2(0.f, 0.f);
+  float lsum = 0.f;  // HEAD_LOSS: this lane's loss contributions
 #pragma unroll
   for (int i = 0; i < FM; ++i)
 #pragma unroll
@@ -422,15 +372,10 @@ __device__ __forceinline__ void run_epilogue_scalar(const GemmParams& p, const f
       for (int r = 0; r < 4; ++r)
         if (rows[i][r].off >= 0 && colok[j]) {
           const float a = fold ? (acc[i][j][r] - ms[i][r].x * colc[j]) * ms[i][r].y : acc[i][j][r];
-          const float* cs = p.coef + 4 * rows[i][r].b;  // mode 4: this row's sample
+          const float* cs = p.coef + 4 * rows[i][r].b;  // HEAD_DDIM_EACH: this row's sample
           const f32x4 cfr = head_ps ? f32x4{cs[0], cs[1], cs[2], cs[3]} : cf;
-          const float o = epilogue<EPI>(p, rows[i][r].off + cols[j], rows[i][r].b, a + colb[j], pre[i][j][r],
-                                        salt_drop, salt_dp, cfr);
-          if (prod) {
-            part[i][r][j / 2] = f2add(part[i][r][j / 2], make_float2(o, o * o));
-            p.xb_out[rows[i][r].off + cols[j]] = f2bf(o);
-          }
-          if (EPI == EPI_HEAD && p.patch_out != nullptr && (p.head_mode == 1 || p.head_mode == 2 || head_ps)) {
+          const float o = epilogue<EPI>(p, rows[i][r].off + cols[j], a + colb[j], pre[i][j][r], cfr);
+          if (HEAD && p.patch_out != nullptr && (p.head_mode == HEAD_DDIM || p.head_mode == HEAD_CLAMP || head_ps)) {
             // the new image pixel (c, a, b) of patch row (sample, token - 1), conv-im2col order
             const int m = mb + i * 16 + 4 * g + r, n = nb + j * 16 + li;
             const int c = n % p.chans, ab = n / p.chans;
@@ -445,27 +390,6 @@ __device__ __forceinline__ void run_epilogue_scalar(const GemmParams& p, const f
         } else if (head_loss && colok[j] && mb + i * 16 + 4 * g + r < p.M) {  // cls rows: zero gradient
           reinterpret_cast<bf16*>(p.C2)[(size_t)(mb + i * 16 + 4 * g + r) * p.N + nb + j * 16 + li] = f2bf(0.f);
         }
-  if (prod) {
-    const int np_out = p.N / LN_SLOT;
-#pragma unroll
-    for (int i = 0; i < FM; ++i)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int sl = 0; sl < (FN + 1) / 2; ++sl) {
-          float2 t = part[i][r][sl];
-          t = f2add(t, f2xor<1>(t));
-          t = f2add(t, f2xor<2>(t));
-          t = f2add(t, f2xor<4>(t));
-          t = f2add(t, f2xor<8>(t));
-          const int m = mb + i * 16 + 4 * g + r;
-          // (a slot past N -- N % 32 == 0, but not a multiple of the wave's columns -- would
-          // be the next row's slot 0)
-          if (li == 0 && m < p.M && nb + sl * LN_SLOT < p.N)
-            *reinterpret_cast<float2*>(p.st_out + 2 * ((size_t)fold_token_row<EPI>(p, m) * np_out + nb / LN_SLOT +
-                                                       sl)) = t;
-        }
-  }
   if (head_loss) {  // one deterministic partial per workgroup (summed by the step tail)
     __shared__ float lred[4];
     lsum = wave_sum(lsum);
@@ -474,7 +398,6 @@ __device__ __forceinline__ void run_epilogue_scalar(const GemmParams& p, const f
     if (threadIdx.x == 0) p.loss_parts[blockIdx.x] = (lred[0] + lred[1]) + (lred[2] + lred[3]);
   }
 }
-
 
 // ---- 4x4 transpose inside each quad of lanes (DPP quad_perm, no LDS):
 // in:  a[r] = element (row r, column x) of a 4x4 block, x = lane's quad position
@@ -525,7 +448,7 @@ __device__ __forceinline__ f32x4 ld4bf(const bf16* p) {
 // Vector epilogue: each lane owns 4 CONSECUTIVE columns of one row, so every
 // load/store of the epilogue is one 8-/16-byte vector access instead of four
 // 2-/4-byte scalar ones.  Requires N % 4 == 0 and output columns contiguous in
-// groups of 4 (all epilogues except HEAD).  Two accumulator layouts:
+// groups of 4 (UsesVecEpi: all epilogues except HEAD and ATOMIC).  Two accumulator layouts:
 //   SW (swapped MFMA operands, the LDS-DMA GEMMs): mfma(B, A) computes C^T, whose
 //     natural layout already is lane = row (li), 4 registers = 4 columns (4g..4g+3)
 //     -- no data movement at all;
@@ -589,6 +512,7 @@ struct VecEpi {
   }
 
   __device__ __forceinline__ void prefetch(const GemmParams& p, int mb, int nb, int g, int li) {
+    static_assert(UsesVecEpi<EPI>::value, "HEAD and ATOMIC take run_epilogue_scalar");
     const int q = sharer(g, li), cs = csub(g, li), rs = rsub(g, li);
     // uniform pointer select + constant-address-space loads -> scalar loads: a vector
     // load under the dropout condition was waited for on the spot (vmcnt(0): the
@@ -601,7 +525,7 @@ struct VecEpi {
     const bool fold = FC && p.ln_st != nullptr;
     first_col = nb == 0 && q == 0;
     colbase = nb;
-    const bool has_bias = (EPI != EPI_ATOMIC) && (EPI != EPI_ACC) && p.bias != nullptr;
+    const bool has_bias = (EPI != EPI_ACC) && p.bias != nullptr;
 #pragma unroll
     for (int j = 0; j < FN; ++j) {
       const int n = nb + j * 16 + cs;
@@ -636,13 +560,13 @@ struct VecEpi {
     if (EPI == EPI_HEADR) {
 #pragma unroll
       for (int i = 0; i < FM; ++i)
-        hcf[i] = p.head_mode == 4 ? ld4(p.coef + 4 * rows[i].b)
-                 : p.head_mode == 1 ? ld4(p.coef) : f32x4{0.f, 1.f, 0.f, 1.f};
+        hcf[i] = p.head_mode == HEAD_DDIM_EACH ? ld4(p.coef + 4 * rows[i].b)
+                 : p.head_mode == HEAD_DDIM ? ld4(p.coef) : f32x4{0.f, 1.f, 0.f, 1.f};
     }
     if (EPI == EPI_HEADRS) {  // rows of 8 floats: {c0, c1, c2, dir} and, in the second 16 bytes, sigma
 #pragma unroll
       for (int i = 0; i < FM; ++i) {
-        const float* cr = p.coef + (p.head_mode == 6 ? 8 * rows[i].b : 0);
+        const float* cr = p.coef + (p.head_mode == HEAD_ETA_EACH ? 8 * rows[i].b : 0);
         hcf[i] = ld4(cr);
         hsg[i] = cr[4];
       }
@@ -679,8 +603,8 @@ struct VecEpi {
           else v = ld4bf(p.aux + rowsafe[i] + ns);
         } else if (PRE && rows[i].off >= 0 && colok[j]) {
           const int n = nb + j * 16 + cs;
-          if (EPI == EPI_HEADR && p.head_mode != 2) v = ld4(p.res + rows[i].off + n);  // x_t
-          if (EPI == EPI_HEADRS) v = ld4(p.res + rows[i].off + n);                      // x_t
+          if ((EPI == EPI_HEADR && p.head_mode != HEAD_CLAMP) || EPI == EPI_HEADRS)
+            v = ld4(p.res + rows[i].off + n);  // x_t
           if (EPI == EPI_HEADL && rows[i].b >= 0)  // target patch row (m - b - 1)
             v = ld4(p.res + (rows[i].off - (rows[i].b + 1) * p.N) + n);
           if (EPI == EPI_ACC && !p.acc_store) v = ld4(reinterpret_cast<const float*>(p.C) + rows[i].off + n);
@@ -696,6 +620,7 @@ struct VecEpi {
   }
 
   __device__ __forceinline__ void finish(const GemmParams& p, const f32x4 (&acc_in)[FM][FN], int li) {
+    static_assert(UsesVecEpi<EPI>::value, "HEAD and ATOMIC take run_epilogue_scalar");
     // every prefetched operand (and the rng words) has long landed: one explicit
     // vmcnt(0) here, BEFORE the first store.  Without it the compiler (operands loaded
     // under conditions, stores under conditions: a path-merged count) waited vmcnt(0)
@@ -756,9 +681,6 @@ struct VecEpi {
           st4bf(reinterpret_cast<bf16*>(p.C) + idx, v);
         } else if (EPI == EPI_F32) {
           st4(reinterpret_cast<float*>(p.C) + idx + blockIdx.z * p.split_stride, v);
-        } else if (EPI == EPI_ATOMIC) {
-#pragma unroll
-          for (int c = 0; c < 4; ++c) atomicAdd(reinterpret_cast<float*>(p.C) + idx + c, v[c]);
         } else if (EPI == EPI_ACC) {
           const f32x4 o = pre[i][j] + v;
           st4(reinterpret_cast<float*>(p.C) + idx, o);
@@ -815,14 +737,14 @@ struct VecEpi {
           }
           st4bf(reinterpret_cast<bf16*>(p.C) + idx, gr);
         } else if (EPI == EPI_HEADR) {
-          // ViT.py:229-234 on the patch rows: x0-hat clamp, then (modes 1 / 4) the DDIM
+          // ViT.py:229-234 on the patch rows: x0-hat clamp, then (HEAD_DDIM / HEAD_DDIM_EACH) the DDIM
           // update with x_t preloaded in `pre`; the new x_t also as the next step's
           // bf16 patch rows (same index: the embedding weight is column-permuted)
           f32x4 x0;
 #pragma unroll
           for (int c = 0; c < 4; ++c) x0[c] = fminf(fmaxf(v[c], -1.f), 1.f);
           f32x4 xn = x0;
-          if (p.head_mode != 2) {
+          if (p.head_mode != HEAD_CLAMP) {
             const f32x4 cf = hcf[i];
 #pragma unroll
             for (int c = 0; c < 4; ++c) xn[c] = cf[2] * x0[c] + cf[3] * ((pre[i][j][c] - cf[0] * x0[c]) / cf[1]);
@@ -848,7 +770,7 @@ struct VecEpi {
           // (4 tiles x 2 ring depths, read in their ISA) fuses x_t - c0 x0 everywhere, c2 x0 +
           // (dir eps) in columns 0 and 1 (v_pk_fma_f32) and not in columns 2 and 3 (two products,
           // v_pk_add_f32).  Left to the compiler here as well, the sum with the noise term was
-          // fused in all four columns: x differed from mode 1's in the last bit of ~1 % of the
+          // fused in all four columns: x differed from HEAD_DDIM's in the last bit of ~1 % of the
           // elements.
           f32x4 xn;
 #pragma unroll
@@ -946,20 +868,11 @@ __device__ __forceinline__ void run_epilogue_vec(const GemmParams& p, const f32x
   ep.finish(p, acc, li);
 }
 
-// epilogues that take the quad-transposed vector path
-template <int EPI>
-struct UsesVecEpi {
-  // HEAD: columns not contiguous.  ATOMIC: in the accumulator layout one atomic
-  // instruction covers 4 rows x 64 B; after the quad transpose it would touch 16
-  // rows (4x the cache lines per instruction) - measured 10% slower per step.
-  static constexpr bool value = EPI != EPI_HEAD && EPI != EPI_ATOMIC;
-};
-
 template <int EPI, int FM, int FN>
 __device__ __forceinline__ void run_epilogue(const GemmParams& p, const f32x4 (&acc)[FM][FN], int mb, int nb,
                                              int g, int li) {
-  if (!UsesVecEpi<EPI>::value) run_epilogue_scalar<EPI, FM, FN>(p, acc, mb, nb, g, li);
-  else run_epilogue_vec<EPI, FM, FN>(p, acc, mb, nb, g, li);
+  if constexpr (UsesVecEpi<EPI>::value) run_epilogue_vec<EPI, FM, FN>(p, acc, mb, nb, g, li);
+  else run_epilogue_scalar<EPI, FM, FN>(p, acc, mb, nb, g, li);
 }
 
 

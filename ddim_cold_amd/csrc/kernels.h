@@ -8,6 +8,21 @@
 #include "gemm_plan.h"
 #include "wgrad_plan.h"
 
+// What a head GEMM's epilogue does with the prediction (GemmArgs::head_mode).  The op schemas
+// pass plain ints; ops/__init__.py names the sampler modes with the same values
+// (tests/test_head_modes_cpu.py reads both).
+enum HeadMode : int {
+  HEAD_IMAGE = 0,      // EPI_HEAD: store it as the [B,C,H,W] image
+  HEAD_DDIM = 1,       // fused DDIM step (res = x_t in, C = x_next, C2 = x0-hat), one coefficient row
+  HEAD_CLAMP = 2,      // x <- clamp(prediction, -1, 1)
+  HEAD_LOSS = 3,       // smooth-L1 loss partials + gradient (res = target)
+  HEAD_DDIM_EACH = 4,  // HEAD_DDIM with one coefficient row per sample
+  HEAD_ETA = 5,        // EPI_HEADRS: DDIM step with noise, one 8-float row {c0, c1, c2, dir, sigma, 0, 0, 0}
+  HEAD_ETA_EACH = 6,   //   one such row per sample
+};
+static_assert(HEAD_IMAGE == 0 && HEAD_DDIM == 1 && HEAD_CLAMP == 2 && HEAD_LOSS == 3, "head modes are op-schema ints");
+static_assert(HEAD_DDIM_EACH == 4 && HEAD_ETA == 5 && HEAD_ETA_EACH == 6, "head modes are op-schema ints");
+
 struct GemmArgs {
   const void* A = nullptr;
   const void* B = nullptr;
@@ -29,12 +44,11 @@ struct GemmArgs {
   const float* temb = nullptr;
   const int64_t* tsteps = nullptr;
   int emb_dim = 0;
-  const float* coef = nullptr;  // EPI_HEAD head_mode 1
-  int head_mode = 0;            // EPI_HEAD: 0 image, 1 fused DDIM step, 2 clamp, 3 smooth-L1 loss + grad
-                                // EPI_HEADRS: 5 one 8-float row {c0, c1, c2, dir, sigma, 0, 0, 0}, 6 one per sample
-  float loss_beta = 1.f;        // EPI_HEAD mode 3
+  const float* coef = nullptr;  // the DDIM modes' coefficient rows
+  int head_mode = HEAD_IMAGE;   // a HeadMode
+  float loss_beta = 1.f;        // HEAD_LOSS
   float loss_inv_n = 1.f;
-  float* loss_parts = nullptr;  // EPI_HEAD mode 3: one partial per workgroup (gemm_nt_grid entries)
+  float* loss_parts = nullptr;  // HEAD_LOSS: one partial per workgroup (gemm_nt_grid entries)
   // EPI_F32 dgrad split over K: slice z of `splits` writes its partial product to
   // C + z * split_stride (no atomics, no zeroing; the consumer sums the slices)
   int splits = 1;
@@ -54,7 +68,7 @@ struct GemmArgs {
   // zeroing) and a bf16 copy of the output to xb_out
   float* st_out = nullptr;
   void* xb_out = nullptr;
-  // sampler steps (GemmParams::patch_out / cls_src): HEAD modes 1/2 also write the new
+  // sampler steps (GemmParams::patch_out / cls_src): the DDIM and clamp head modes also write the new
   // image as bf16 patch rows; EMBED writes the cls rows itself (no patchify launch)
   void* patch_out = nullptr;
   const float* cls_src = nullptr;

@@ -267,7 +267,7 @@ SITE_STEP_NOISE = 4096
 SITE_PASTE_NOISE = 8192
 SITE_JUMP_NOISE = 12288
 SITE_LOOP_FORWARDS = 4096
-# head-step modes (the values csrc/bindings.cpp and csrc/gemm_epi.h test): clamp + DDIM update
+# head-step modes (csrc/kernels.h enum HeadMode, same names and values): clamp + DDIM update
 # with one coefficient row / clamp only / DDIM with one row per sample / the stochastic
 # (eta > 0) DDIM step with one row of 8 / with one row of 8 per sample
 HEAD_DDIM, HEAD_CLAMP, HEAD_DDIM_EACH, HEAD_ETA, HEAD_ETA_EACH = 1, 2, 4, 5, 6
