@@ -19,11 +19,17 @@ inline int grid_for(int64_t n8) {
   int64_t b = (n8 + kThreads - 1) / kThreads;
   return (int)(b < 1 ? 1 : (b > kMaxBlocks ? kMaxBlocks : b));
 }
+
+// both sides move 16-byte vectors (two float4 and one bf16x8 per lane); pointers that are
+// not aligned for them take the kernels' scalar loop (the decision adamw_launch makes)
+inline bool aligned16(const void* a, const void* b) {
+  return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15) == 0;
+}
 }  // namespace
 
 __global__ __launch_bounds__(kThreads) void wire_pack_kernel(const float* __restrict__ src, bf16* __restrict__ dst,
-                                                             int64_t n) {
-  const int64_t n8 = n / 8;
+                                                             int64_t n, bool vec) {
+  const int64_t n8 = vec ? n / 8 : 0;
   const int64_t stride = (int64_t)gridDim.x * kThreads;
   for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n8; i += stride) {
     const float4 a = reinterpret_cast<const float4*>(src)[2 * i];
@@ -33,22 +39,21 @@ __global__ __launch_bounds__(kThreads) void wire_pack_kernel(const float* __rest
     o[4] = f2bf(b.x); o[5] = f2bf(b.y); o[6] = f2bf(b.z); o[7] = f2bf(b.w);
     reinterpret_cast<bf16x8*>(dst)[i] = o;
   }
-  // tail (n not a multiple of 8): one thread of block 0
-  if (blockIdx.x == 0 && threadIdx.x == 0)
-    for (int64_t j = n8 * 8; j < n; ++j) dst[j] = f2bf(src[j]);
+  // tail (n not a multiple of 8), or everything when the pointers are not 16-byte aligned
+  // (`vec` is checked on the host): one element per lane, grid-strided
+  for (int64_t j = n8 * 8 + (int64_t)blockIdx.x * kThreads + threadIdx.x; j < n; j += stride) dst[j] = f2bf(src[j]);
 }
 
 __global__ __launch_bounds__(kThreads) void wire_unpack_kernel(const bf16* __restrict__ src, float* __restrict__ dst,
-                                                               int64_t n) {
-  const int64_t n8 = n / 8;
+                                                               int64_t n, bool vec) {
+  const int64_t n8 = vec ? n / 8 : 0;
   const int64_t stride = (int64_t)gridDim.x * kThreads;
   for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n8; i += stride) {
     const bf16x8 v = reinterpret_cast<const bf16x8*>(src)[i];
     reinterpret_cast<float4*>(dst)[2 * i] = make_float4(bf2f(v[0]), bf2f(v[1]), bf2f(v[2]), bf2f(v[3]));
     reinterpret_cast<float4*>(dst)[2 * i + 1] = make_float4(bf2f(v[4]), bf2f(v[5]), bf2f(v[6]), bf2f(v[7]));
   }
-  if (blockIdx.x == 0 && threadIdx.x == 0)
-    for (int64_t j = n8 * 8; j < n; ++j) dst[j] = bf2f(src[j]);
+  for (int64_t j = n8 * 8 + (int64_t)blockIdx.x * kThreads + threadIdx.x; j < n; j += stride) dst[j] = bf2f(src[j]);
 }
 
 // Bucket hand-off signal of the event-split data-parallel step (engine.py,
@@ -185,10 +190,11 @@ void flag_bump_launch(void* flags, int k, hipStream_t stream) {
 
 void wire_pack_launch(const float* src, void* dst, int64_t n, hipStream_t stream) {
   if (n <= 0) return;
-  wire_pack_kernel<<<grid_for(n / 8), kThreads, 0, stream>>>(src, reinterpret_cast<bf16*>(dst), n);
+  wire_pack_kernel<<<grid_for(n / 8), kThreads, 0, stream>>>(src, reinterpret_cast<bf16*>(dst), n, aligned16(src, dst));
 }
 
 void wire_unpack_launch(const void* src, float* dst, int64_t n, hipStream_t stream) {
   if (n <= 0) return;
-  wire_unpack_kernel<<<grid_for(n / 8), kThreads, 0, stream>>>(reinterpret_cast<const bf16*>(src), dst, n);
+  wire_unpack_kernel<<<grid_for(n / 8), kThreads, 0, stream>>>(reinterpret_cast<const bf16*>(src), dst, n,
+                                                               aligned16(src, dst));
 }

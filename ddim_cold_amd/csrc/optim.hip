@@ -42,10 +42,12 @@ __device__ __forceinline__ int64_t lazy_map(int64_t j, int64_t lo4, int64_t len4
 }
 
 __global__ __launch_bounds__(256) void sqnorm_kernel(const float* __restrict__ g, int64_t n, float* out, float scale,
-                                                     int64_t lo4, int64_t len4) {
+                                                     int64_t lo4, int64_t len4, bool vec) {
   __shared__ float red[4];
   float acc = 0.f;
-  const int64_t n4 = n / 4, nc4 = n4 - len4;
+  // `vec` is checked on the host (16-byte aligned g); without it every element takes the
+  // scalar loop below, which then also steps over the lazy range
+  const int64_t n4 = vec ? n / 4 : 0, nc4 = vec ? n4 - len4 : 0;
   const float4* g4 = reinterpret_cast<const float4*>(g);
   // four independent 16-byte loads in flight per thread before any use
   const int64_t st = (int64_t)gridDim.x * 256;
@@ -61,8 +63,10 @@ __global__ __launch_bounds__(256) void sqnorm_kernel(const float* __restrict__ g
     const float4 v = g4[lazy_map(i, lo4, len4)];
     acc += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
   }
-  for (int64_t i = n4 * 4 + (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+  for (int64_t i = n4 * 4 + (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    if (i >= 4 * lo4 && i < 4 * (lo4 + len4)) continue;  // (never true past n4 * 4 on the vector path)
     acc += g[i] * g[i];
+  }
   acc = wave_sum(acc);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
   __syncthreads();
@@ -213,7 +217,9 @@ void sqnorm_launch(const float* g, int64_t n, float* out, int nparts, float scal
                    int64_t lz_lo, int64_t lz_hi) {
   check_lazy(n, lz_lo, lz_hi);
   const int64_t len4 = lz_hi > lz_lo ? (lz_hi - lz_lo) / 4 : 0;
-  hipLaunchKernelGGL(sqnorm_kernel, dim3(nparts), dim3(256), 0, stream, g, n, out, scale, lz_lo / 4, len4);
+  const bool vec = (reinterpret_cast<uintptr_t>(g) & 15) == 0;  // else the scalar path (as adamw_launch)
+  hipLaunchKernelGGL(sqnorm_kernel, dim3(nparts), dim3(256), 0, stream, g, n, out, scale, len4 ? lz_lo / 4 : 0, len4,
+                     vec);
 }
 
 void adamw_launch(float* p, float* g, float* m, float* v, void* p_bf16, int64_t n, const float* sqnorm,

@@ -401,6 +401,8 @@ def wire_pack(src, dst):
     """fp32 -> bf16 (round to nearest even) into ``dst`` (gradient wire format)."""
     if _hip(src):
         return _ops().wire_pack(src, dst)
+    if src.numel() != dst.numel():
+        raise RuntimeError("wire_pack: sizes")
     dst.copy_(src)
 
 
@@ -408,6 +410,8 @@ def wire_unpack(src, dst):
     """bf16 -> fp32 into ``dst``."""
     if _hip(src):
         return _ops().wire_unpack(src, dst)
+    if src.numel() != dst.numel():
+        raise RuntimeError("wire_unpack: sizes")
     dst.copy_(src)
 
 
@@ -697,12 +701,19 @@ def sq_parts_size(n_tiles: int) -> int:
 def sqnorm(g, out, scale: float = 1.0, lazy=None):
     """Per-block partial sums of (g*scale)^2 into ``out`` (>= SQ_PARTS floats, a multiple
     of 256, fully overwritten).
-    ``lazy`` = (lo, hi): an arena range whose gradient is identically zero (skipped)."""
+    ``lazy`` = (lo, hi): an arena range whose gradient is identically zero (skipped: not
+    read; whole 16-byte vectors inside the arena, anything else raises)."""
     lo, hi = lazy if lazy is not None else (0, 0)
     if _hip(g):
         return _ops().sqnorm(g, out, float(scale), int(lo), int(hi))
+    n = g.numel()
+    if hi > lo and (lo < 0 or hi > n // 4 * 4 or lo % 4 or hi % 4):
+        raise RuntimeError("optimizer lazy range must be whole 16-B vectors inside the arena")
+    flat = g.reshape(-1).float()
+    if hi > lo:
+        flat = torch.cat((flat[:lo], flat[hi:]))
     out.zero_()
-    out[0] = (g.float() * scale).pow(2).sum()
+    out[0] = (flat * scale).pow(2).sum()
 
 
 def weight_ema_decay(decay: float, t: int, warmup: bool) -> torch.Tensor:
@@ -749,7 +760,9 @@ def adamw_step(p, g, m, v, pbf, sq, step, hyper, grad_scale: float = 1.0, zero_h
     if max_norm > 0:
         coef *= min(1.0, max_norm / (math.sqrt(sqv) + 1e-6)) if math.isfinite(sqv) else 1.0
     gi = g * coef
+    g_lazy = g[lo:hi].clone()  # the lazy range is not touched, its gradient included
     g[: (g.numel() if zero_hi is None else zero_hi)].zero_()
+    g[lo:hi] = g_lazy
     if not math.isfinite(sqv):
         return
     t = int(step[0]) + 1
@@ -767,7 +780,9 @@ def adamw_step(p, g, m, v, pbf, sq, step, hyper, grad_scale: float = 1.0, zero_h
     if hi > lo:
         p[lo:hi], m[lo:hi], v[lo:hi] = keep
     if pbf is not None:
+        pb_lazy = pbf[lo:hi].clone()
         pbf.copy_(p.to(torch.bfloat16))
+        pbf[lo:hi] = pb_lazy
     if ema is not None:  # e <- p + d (e - p): sub, mul, add, each rounded to fp32
         d = weight_ema_decay(ema_decay, t - 1, ema_warmup).to(p.device)
         ema.sub_(p).mul_(d).add_(p)
