@@ -63,18 +63,25 @@ def _inpaint(model, device, image_file, mask_file, k, eta, resample, seed, gener
               "--ckpt, else the <ckpt>_ema sibling file (bestloss.pkl -> bestloss_ema.pkl)")
 @click.option("--eta", default=0.0, type=float, help="DDIM noise scale in [0, 1]: 0 deterministic DDIM (default), "
               "1 DDPM ancestral sampling; applies to the trajectory grid and the samples")
+@click.option("--solver", default="ddim", help="ddim (default), or dpmpp2m: DPM-Solver++(2M), the second-order "
+              "multistep solver on the same --acc_k grid (needs --eta 0; not used by --inpaint)")
 @click.option("--inpaint", "inpaint_image", default=None, metavar="IMAGE", help="inpaint IMAGE instead of sampling: "
               "keep it where --mask is white, generate the rest (jump --acc_k, noise --eta, --seed); writes "
               "inpaint.png = original | masked input | result")
 @click.option("--mask", "mask_file", default=None, metavar="MASK", help="mask picture of --inpaint (white = keep); "
               "default: a centred square hole of half the image size")
 @click.option("--resample", default=1, help="--inpaint: runs of every grid step (RePaint resampling), >= 1")
-def main(sample_n, acc_k, ckpt, model_name, out_dir, seq_n, seq_k, seed, ema, eta, inpaint_image, mask_file, resample):
+def main(sample_n, acc_k, ckpt, model_name, out_dir, seq_n, seq_k, seed, ema, eta, solver, inpaint_image, mask_file,
+         resample):
     """DDIM sampling from a DiffusionVisionTransformer checkpoint."""
     from ddim_cold_amd.models import build_model
     from ddim_cold_amd.train.checkpoint import load_weights, resolve_ema_checkpoint
     if not 0.0 <= eta <= 1.0:
         sys.exit(f"error: --eta must be in [0, 1], got {eta}")
+    if solver not in ("ddim", "dpmpp2m"):
+        sys.exit(f"error: --solver must be ddim or dpmpp2m, got {solver}")
+    if solver == "dpmpp2m" and eta > 0:
+        sys.exit(f"error: --solver dpmpp2m needs --eta 0, got {eta}")
     if resample < 1:
         sys.exit(f"error: --resample must be >= 1, got {resample}")
     device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
@@ -95,9 +102,9 @@ def main(sample_n, acc_k, ckpt, model_name, out_dir, seq_n, seq_k, seed, ema, et
     if inpaint_image is not None:
         print(f"wrote {_inpaint(model, device, inpaint_image, mask_file, acc_k, eta, resample, seed, g, out_dir)}")
         return
-    seq = model.diffusion_sequence(device, seq_k, N=seq_n, generator=g, eta=eta)
+    seq = model.diffusion_sequence(device, seq_k, N=seq_n, generator=g, eta=eta, solver=solver)
     p1 = save_sequence_grid(seq, get_next_path(os.path.join(out_dir, "denoise_sequence.png")))
-    imgs = model.sampler(device, acc_k, sample_n, generator=g, eta=eta)
+    imgs = model.sampler(device, acc_k, sample_n, generator=g, eta=eta, solver=solver)
     p2 = save_grid(imgs, get_next_path(os.path.join(out_dir, "samples.png")), nrow=16)
     print(f"wrote {p1} and {p2}")
 

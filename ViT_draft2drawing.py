@@ -41,6 +41,9 @@ def main(argv=None):
     ap.add_argument("--eta", type=float, default=0.0,
                     help="DDIM noise scale of the draft -> drawing stage, in [0, 1]: 0 deterministic DDIM "
                          "(default), 1 DDPM ancestral sampling")
+    ap.add_argument("--solver", choices=("ddim", "dpmpp2m"), default="ddim",
+                    help="solver of the draft -> drawing stage: ddim (default), or dpmpp2m = DPM-Solver++(2M), "
+                         "second-order multistep on the same grid (needs --eta 0)")
     ap.add_argument("--predict", choices=("prev", "x0"), default="prev",
                     help="what the cold model predicts: x_{t-1} (dataset: cold) or x0 (dataset: cold_x0)")
     ap.add_argument("--algorithm", type=int, choices=(1, 2), default=2,
@@ -50,6 +53,8 @@ def main(argv=None):
     a = ap.parse_args(argv)
     if not 0.0 <= a.eta <= 1.0:
         ap.error(f"--eta must be in [0, 1], got {a.eta}")
+    if a.solver == "dpmpp2m" and a.eta > 0:
+        ap.error(f"--solver dpmpp2m needs --eta 0, got {a.eta}")
     from ddim_cold_amd.data.datasets import load_image
     from ddim_cold_amd.data.synthetic import synthetic_pool
     from ddim_cold_amd.diffusion.samplers import img2img
@@ -98,7 +103,7 @@ def main(argv=None):
         print(f"warning: {a.draft} not found, using a synthetic draft", file=sys.stderr)
         draft = synthetic_pool(1, tuple(model.img_size), seed=a.seed)[0]
     starts = list(range(1599, 2000, 50))
-    out = img2img(model, draft, starts, k=a.k, device=device, generator=g, eta=a.eta)
+    out = img2img(model, draft, starts, k=a.k, device=device, generator=g, eta=a.eta, solver=a.solver)
     row = torch.cat([((draft + 1) / 2).unsqueeze(0), out], dim=0)
     p2 = save_grid(row, get_next_path(os.path.join(a.out_dir, "draft2img.png")), nrow=row.shape[0])
     print(f"wrote {p1} and {p2}")

@@ -1189,6 +1189,39 @@ void repaint_rows_(Tensor x, Tensor known, Tensor mask, Tensor coef, Tensor rng,
                       rng.data_ptr<int64_t>(), (int)site_paste, (int)site_jump, po, n, cur_stream());
 }
 
+// DPM-Solver++(2M) step on the sampler's patch rows (csrc/diffusion.hip dpm2m_rows_kernel), in
+// place on x; every check before the launch.
+void dpm2m_rows_(Tensor x, Tensor x0, Tensor x0_prev, Tensor coef, int64_t batch, bool each,
+                 c10::optional<Tensor> patches_out) {
+  CHECK_IN(x, F32); CHECK_IN(x0, F32); CHECK_IN(x0_prev, F32); CHECK_IN(coef, F32);
+  const c10::DeviceGuard guard(x.device());
+  TORCH_CHECK(x0.device() == x.device() && x0_prev.device() == x.device() && coef.device() == x.device(),
+              "dpm2m_rows_: x, x0, x0_prev and coef on one device");
+  TORCH_CHECK(x0.sizes() == x.sizes() && x0_prev.sizes() == x.sizes(), "dpm2m_rows_: x, x0 and x0_prev of one shape");
+  const int64_t n = x.numel();
+  TORCH_CHECK(batch >= 1 && batch <= INT32_MAX, "dpm2m_rows_: batch must be a positive int");
+  TORCH_CHECK(n % (4 * batch) == 0, "dpm2m_rows_: the element count must be a multiple of 4 * batch");
+  TORCH_CHECK(n < ((int64_t)1 << 31), "dpm2m_rows_: 32-bit indexing needs fewer than 2^31 elements");
+  TORCH_CHECK(coef.numel() == (each ? 8 * batch : 8),
+              "dpm2m_rows_: coef must hold one row {c0, c1, c2, c3, g, 0, 0, 0}, or (each) one per sample");
+  const char *xp = (const char*)x.data_ptr(), *sp = (const char*)x0.data_ptr(), *pp = (const char*)x0_prev.data_ptr();
+  TORCH_CHECK((xp + n * 4 <= sp || sp + n * 4 <= xp) && (xp + n * 4 <= pp || pp + n * 4 <= xp),
+              "dpm2m_rows_: x must not alias x0 or x0_prev");
+  TORCH_CHECK((uintptr_t)xp % 16 == 0 && (uintptr_t)sp % 16 == 0 && (uintptr_t)pp % 16 == 0,
+              "dpm2m_rows_: x, x0 and x0_prev must be 16-byte aligned");
+  void* po = nullptr;
+  if (given(patches_out)) {
+    CHECK_IN((*patches_out), BF16);
+    TORCH_CHECK(patches_out->device() == x.device() && patches_out->sizes() == x.sizes(),
+                "dpm2m_rows_: patches_out must be on x's device and of its shape");
+    po = patches_out->data_ptr();
+    TORCH_CHECK((uintptr_t)po % 8 == 0, "dpm2m_rows_: patches_out must be 8-byte aligned");
+  }
+  if (n == 0) return;
+  dpm2m_rows_launch(x.data_ptr<float>(), x0.data_ptr<float>(), x0_prev.data_ptr<float>(), coef.data_ptr<float>(),
+                    (int)batch, each, po, n, cur_stream());
+}
+
 void randn_(Tensor out, Tensor rng, int64_t site) {
   CHECK_IN(out, F32); check_rng(rng);
   const c10::DeviceGuard guard(out.device());
@@ -1383,6 +1416,8 @@ TORCH_LIBRARY(ddim_cold, m) {
         "int algorithm, Tensor(b!)? patches_out) -> ()");
   m.def("repaint_rows_(Tensor(a!) x, Tensor known, Tensor mask, Tensor coef, Tensor rng, int site_paste, "
         "int site_jump, Tensor(b!)? patches_out) -> ()");
+  m.def("dpm2m_rows_(Tensor(a!) x, Tensor x0, Tensor x0_prev, Tensor coef, int batch, bool each, "
+        "Tensor(b!)? patches_out) -> ()");
   m.def("randn_(Tensor(a!) out, Tensor rng, int site) -> ()");
   m.def("q_sample(Tensor x0, Tensor t, Tensor eps, int total_steps) -> Tensor");
   m.def("pixelate_pair(Tensor img, Tensor? idx, Tensor t, int B) -> (Tensor, Tensor)");
@@ -1433,6 +1468,7 @@ TORCH_LIBRARY_IMPL(ddim_cold, CUDA, m) {
   m.impl("cold_step_", &cold_step_);
   m.impl("cold_step_rows_", &cold_step_rows_);
   m.impl("repaint_rows_", &repaint_rows_);
+  m.impl("dpm2m_rows_", &dpm2m_rows_);
   m.impl("randn_", &randn_);
   m.impl("q_sample", &q_sample);
   m.impl("pixelate_pair", &pixelate_pair);

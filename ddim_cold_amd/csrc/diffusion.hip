@@ -14,6 +14,8 @@
 //  * cold_step / repaint_rows: the per-step launches of the cold x0 sampler and of inpainting
 //    (paste the kept region at the step's noise level, jump back for a resample), in place
 //    on the sampler state.
+//  * dpm2m_rows: the per-step launch of the DPM-Solver++(2M) sampler (the DDIM update plus
+//    one term from the previous step's x0-hat), in place on the patch-row state.
 #include "common.h"
 #include "kernels.h"
 
@@ -265,6 +267,51 @@ __global__ __launch_bounds__(256) void repaint_rows_kernel(float* __restrict__ x
   }
 }
 
+// DPM-Solver++(2M) step (Lu et al. 2022) of an x0-predicting model, in place on the sampler's
+// fp32 patch-row state x, after the forward that wrote the clamped x0-hat (HEAD_CLAMP) into x0;
+// x0p is the previous step's x0-hat.  Per element, every rounding as written:
+//   de  = rounded(c3 * (fma(-c0, x0, x) / c1))
+//   det = fma(c2, x0, de)                                   (the DDIM step)
+//   out = g == 0 ? det : fma(g, rounded(x0 - x0p), det)     (the second-order term)
+// coef = rows {c0, c1, c2, c3, g, 0, 0, 0} from device memory (schedule.dpm2m_row; a captured
+// loop has no host scalars): one row (each = 0), or one per sample [B][8] (each = 1), the sample
+// of 4-vector q being q / per4 (per4 = elements per sample / 4, so a thread's 4 elements share
+// one row).  A row with g == 0 never loads x0p (wave-uniform for each = 0, a branch on the
+// thread's row otherwise): a sample's first step has no history to read.  Each thread owns 4
+// consecutive elements: 16-byte loads of x / x0 / x0p, a 16-byte store of x and an 8-byte
+// store of its bf16 rows (pout, optional).  n4 = elements / 4 (elements < 2^31).
+__global__ __launch_bounds__(256) void dpm2m_rows_kernel(float* __restrict__ x, const float* __restrict__ x0,
+                                                         const float* __restrict__ x0p,
+                                                         const float* __restrict__ coef, int each, int per4,
+                                                         bf16* __restrict__ pout, int n4) {
+  float c0 = coef[0], c1 = coef[1], c2 = coef[2], c3 = coef[3], g = coef[4];
+  for (int q = blockIdx.x * 256 + threadIdx.x; q < n4; q += gridDim.x * 256) {
+    const int e = 4 * q;
+    if (each) {
+      const float* cf = coef + (q / per4) * 8;
+      c0 = cf[0]; c1 = cf[1]; c2 = cf[2]; c3 = cf[3]; g = cf[4];
+    }
+    f32x4 v = *reinterpret_cast<const f32x4*>(x + e);
+    const f32x4 p = *reinterpret_cast<const f32x4*>(x0 + e);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float de = rounded(c3 * (__builtin_fmaf(-c0, p[j], v[j]) / c1));
+      v[j] = __builtin_fmaf(c2, p[j], de);
+    }
+    if (g != 0.f) {
+      const f32x4 pp = *reinterpret_cast<const f32x4*>(x0p + e);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v[j] = __builtin_fmaf(g, rounded(p[j] - pp[j]), v[j]);
+    }
+    *reinterpret_cast<f32x4*>(x + e) = v;
+    if (pout != nullptr) {
+      bf16x4 h;
+      h[0] = f2bf(v[0]); h[1] = f2bf(v[1]); h[2] = f2bf(v[2]); h[3] = f2bf(v[3]);
+      *reinterpret_cast<bf16x4*>(pout + e) = h;
+    }
+  }
+}
+
 static int g_grid(int64_t n) {
   int64_t g = (n + 255) / 256;
   if (g > 4096) g = 4096;
@@ -296,6 +343,12 @@ void repaint_rows_launch(float* x, const float* known, const uint8_t* mask, cons
                          int site_paste, int site_jump, void* patches_out, int64_t n, hipStream_t stream) {
   hipLaunchKernelGGL(repaint_rows_kernel, dim3(g_grid(n / 4)), dim3(256), 0, stream, x, known, mask, coef, rng,
                      site_paste, site_jump, reinterpret_cast<bf16*>(patches_out), (int)(n / 4));
+}
+
+void dpm2m_rows_launch(float* x, const float* x0, const float* x0_prev, const float* coef, int batch, bool each,
+                       void* patches_out, int64_t n, hipStream_t stream) {
+  hipLaunchKernelGGL(dpm2m_rows_kernel, dim3(g_grid(n / 4)), dim3(256), 0, stream, x, x0, x0_prev, coef, each ? 1 : 0,
+                     (int)(n / 4 / batch), reinterpret_cast<bf16*>(patches_out), (int)(n / 4));
 }
 
 void randn_launch(float* out, int64_t n, const int64_t* rng, int site, hipStream_t stream) {

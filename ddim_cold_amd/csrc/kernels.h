@@ -306,6 +306,12 @@ void cold_step_launch(float* x, const float* x0, const int64_t* t, void* patches
 // patches_out (optional): bf16 of what was written.  n = elements, n % 4 == 0, n < 2^31.
 void repaint_rows_launch(float* x, const float* known, const uint8_t* mask, const float* coef, const int64_t* rng,
                          int site_paste, int site_jump, void* patches_out, int64_t n, hipStream_t stream);
+// DPM-Solver++(2M) step in place on the fp32 patch rows x: x <- c2 x0 + c3 (x - c0 x0) / c1 +
+// g (x0 - x0_prev) from device rows {c0, c1, c2, c3, g, 0, 0, 0}: one row, or (each) one per
+// sample [batch][8]; a row with g == 0 is the DDIM step and never reads x0_prev.  patches_out
+// (optional): bf16 of what was written.  n = elements, n % (4 batch) == 0, n < 2^31.
+void dpm2m_rows_launch(float* x, const float* x0, const float* x0_prev, const float* coef, int batch, bool each,
+                       void* patches_out, int64_t n, hipStream_t stream);
 void randn_launch(float* out, int64_t n, const int64_t* rng, int site, hipStream_t stream);
 void q_sample_launch(const float* x0, const int64_t* t, const float* eps, float* out, int B, int64_t per,
                      int total_steps, hipStream_t stream);

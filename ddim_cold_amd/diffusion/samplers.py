@@ -21,7 +21,9 @@ update, cold clamp, or img2img's DDIM update with per-sample coefficients) and
 hands the next step its bf16 patch rows; the cold sampler of an x0-predicting model
 (``ColdSampler(predict="x0")``) instead follows each forward with one
 :func:`ops.cold_step_` launch, and inpainting (:func:`inpaint`) each forward with one
-:func:`ops.repaint_rows_` launch that pastes the kept region back.  (Splitting a batch into concurrent
+:func:`ops.repaint_rows_` launch that pastes the kept region back, and the DPM-Solver++(2M)
+solver (``DDIMSampler(solver="dpmpp2m")``) each forward with one :func:`ops.dpm2m_rows_` launch
+that applies the second-order multistep update.  (Splitting a batch into concurrent
 chains on separate streams measured slower on MI355X -- ViT-tiny N=64 k=20:
 46.9 / 56.2 / 76.2 ms for 1 / 2 / 4 chains -- and was removed.)
 """
@@ -35,7 +37,7 @@ import torch
 from .. import ops
 from ..models.program import HeadStep, fold_width_ok, model_tensors
 from .schedule import (ETA_IDENT_ROW, cold_steps, ddim_coefficients, ddim_coefficients_eta, ddim_table,
-                       ddim_table_eta, eta_row, img2img_alpha, repaint_table)
+                       ddim_table_eta, dpm2m_row, dpm2m_step_h, dpm2m_table, eta_row, img2img_alpha, repaint_table)
 
 
 def _use_fused(model, device) -> bool:
@@ -128,7 +130,24 @@ def _patch_rows(model, N: int, device, den) -> Optional[torch.Tensor]:
 ROWS = True
 
 
-class _Rows:
+class _History:
+    """The x0-hat history of a multistep loop (DPM-Solver++(2M)): ``x0`` is the buffer the
+    step's forward writes, ``x0_prev`` the one the step before wrote, and the two trade places
+    between steps.  The loop is unrolled at capture, so the swap renames two buffers: no copy,
+    no store."""
+
+    def history(self, steps: int):
+        """Start a loop of ``steps`` steps: the last one writes the state's own ``x0``."""
+        if getattr(self, "_x0_pair", None) is None:
+            self._x0_pair = (self.x0, torch.zeros_like(self.x0))
+        a, b = self._x0_pair
+        self.x0, self.x0_prev = (a, b) if steps % 2 else (b, a)
+
+    def swap_x0(self):
+        self.x0, self.x0_prev = self.x0_prev, self.x0
+
+
+class _Rows(_History):
     """Patch-row state of one captured sampling loop (GPU fused path only).
 
     Inside the loop: :meth:`begin` converts the [N, C, H, W] start image once and
@@ -174,6 +193,11 @@ class _Rows:
         """Inpainting mask step on ``x`` (``known`` / ``mask`` as patch rows), its bf16 rows into ``pin``."""
         ops.repaint_rows_(self.x, known, mask, coef, rng, site_paste, site_jump, patches_out=self.pin)
 
+    def dpm_step(self, coef, each: bool):
+        """``x`` <- DPM-Solver++(2M) step from ``x0`` / ``x0_prev`` (``coef``: one row of 8, or
+        ``each``: one per sample), and its bf16 rows into ``pin``."""
+        ops.dpm2m_rows_(self.x, self.x0, self.x0_prev, coef, self.shape[0], each, patches_out=self.pin)
+
     def image(self, xr):
         return ops.rows_to_image(xr, *self.shape, self.p)
 
@@ -184,7 +208,7 @@ class _Rows:
             x.copy_(self.image(self.x))
 
 
-class _Image:
+class _Image(_History):
     """Image-layout state of one sampling loop, with the interface of :class:`_Rows` (the
     CPU, ``ROWS`` / ``PATCH_CHAIN`` off, a stochastic loop of the unfolded program): ``x`` and
     ``x0`` are the loop's own [N, C, H, W] buffers (``x0`` None: one of its own), so nothing
@@ -221,6 +245,13 @@ class _Image:
         layout around the op, as :meth:`_StepNoise.add_`'s noise does (a loop without a chain)."""
         xr = ops.image_to_rows(self.x, self.p).contiguous()
         ops.repaint_rows_(xr, known, mask, coef, rng, site_paste, site_jump)
+        self.x.copy_(ops.rows_to_image(xr, *self.x.shape, self.p))
+
+    def dpm_step(self, coef, each: bool):
+        """DPM-Solver++(2M) step: ``x`` / ``x0`` / ``x0_prev`` go through the row layout around
+        the op, as in :meth:`repaint` (a loop without a chain)."""
+        xr, x0, x0p = (ops.image_to_rows(v, self.p).contiguous() for v in (self.x, self.x0, self.x0_prev))
+        ops.dpm2m_rows_(xr, x0, x0p, coef, self.x.shape[0], each)
         self.x.copy_(ops.rows_to_image(xr, *self.x.shape, self.p))
 
     def image(self, xr):
@@ -261,6 +292,29 @@ def _ddim_step(s, coef, each: bool, nz):
         s.step(t, mode, coef4[i])
         nz.add_(s.x, i, sigma[i])
     return step
+
+
+def _dpm_step(s, coef, each: bool):
+    """``step(i, t)`` of DPM-Solver++(2M) on the state ``s`` (after ``s.history(steps)``): one
+    forward that writes the clamped x0-hat (``x`` untouched), then one :func:`ops.dpm2m_rows_`
+    launch with table row ``coef[i]`` (rows of 8; ``each``: one per sample) that reads it and the
+    x0-hat of the step before; the two x0 buffers trade places from step to step."""
+    def step(i, t):
+        if i:
+            s.swap_x0()
+        s.predict_x0(t)
+        s.dpm_step(coef[i], each)
+    return step
+
+
+SOLVERS = ("ddim", "dpmpp2m")
+
+
+def _check_solver(solver, eta: float):
+    if solver not in SOLVERS:
+        raise ValueError(f"solver must be one of {SOLVERS}, got {solver!r}")
+    if solver == "dpmpp2m" and float(eta) > 0:
+        raise ValueError("solver='dpmpp2m' is the deterministic ODE solver: eta must be 0 (no SDE variant)")
 
 
 def _step_times(ts, N: int, device) -> torch.Tensor:
@@ -400,9 +454,18 @@ class DDIMSampler:
     to rounding, two more launches per step, no patch-row chain.
 
     The seed of a run's noise is one ``torch.randint`` from ``generator`` after x_T is drawn
-    (``noise_seed=`` overrides it); with ``eta`` = 0 nothing extra is drawn."""
+    (``noise_seed=`` overrides it); with ``eta`` = 0 nothing extra is drawn.
 
-    def __init__(self, model, device, k: int = 10, use_graph: bool = True, eta: float = 0.0):
+    ``solver="dpmpp2m"``: DPM-Solver++(2M) (Lu et al. 2022) on the same timestep grid, the
+    second-order multistep solver for x0-predicting models whose first-order member is DDIM
+    (``schedule.dpm2m_row``).  A step is one forward that leaves the clamped x0-hat in its own
+    buffer plus one :func:`ops.dpm2m_rows_` launch, which adds ``g (x0 - x0_prev)`` to the DDIM
+    update and writes the next step's bf16 patch rows; it needs ``eta`` = 0.  The loops of the
+    two solvers are cached under keys of different kinds."""
+
+    def __init__(self, model, device, k: int = 10, use_graph: bool = True, eta: float = 0.0, solver: str = "ddim"):
+        _check_solver(solver, eta)
+        self.solver = solver
         self.model = model
         self.device = torch.device(device)
         self.k = k
@@ -412,6 +475,8 @@ class DDIMSampler:
         self.ts, coef = ddim_table(self.T, k, device=self.device)
         self.coef = coef
         self.coef8 = ddim_table_eta(self.T, k, self.eta, device=self.device)[1] if self.eta > 0 else None
+        if solver == "dpmpp2m":
+            self.coef8 = dpm2m_table(self.T, k, device=self.device)[1]
         self.use_graph = use_graph and self.device.type == "cuda"
         self.H, self.W = model.img_size
         self.C = model.in_chans
@@ -421,6 +486,8 @@ class DDIMSampler:
         key = ("ddim", N, self.k, record, str(self.device))
         if self.eta > 0:
             key = ("ddim_eta", N, self.k, record, str(self.device), self.eta)
+        if self.solver == "dpmpp2m":
+            key = ("ddim_dpm", N, self.k, record, str(self.device))
         return _cached_loop(self.model, key, lambda: self._build(N, record))
 
     def _build(self, N: int, record: bool) -> _LoopState:
@@ -431,13 +498,19 @@ class DDIMSampler:
         tt = _step_times(self.ts, N, dev)
         traj = torch.zeros(len(self.ts), N, self.C, self.H, self.W, device=dev) if record else None
         nz = _StepNoise(self.model, N, dev) if self.eta > 0 else None
-        s = _loop_state(self.model, N, dev, den, x, x0, eta=nz is not None)
-        step = _ddim_step(s, self.coef if nz is None else self.coef8, False, nz)
+        dpm = self.solver == "dpmpp2m"
+        s = _loop_state(self.model, N, dev, den, x, x0, eta=nz is not None, chain=not dpm)
+        if dpm:
+            step = _dpm_step(s, self.coef8, False)
+        else:
+            step = _ddim_step(s, self.coef if nz is None else self.coef8, False, nz)
 
         def loop():
             s.begin(x)
+            if dpm:
+                s.history(len(self.ts))
             for i in range(len(self.ts)):
-                step(i, tt[i])  # forward + clamp + DDIM update, one head epilogue
+                step(i, tt[i])  # forward + clamp + DDIM update, one head epilogue (2M: + one launch)
                 if traj is not None:
                     traj[i].copy_(s.image(s.x0))
             s.write_back(x0=x0)  # (x_t itself is not returned)
@@ -657,21 +730,42 @@ def starts_table_eta(total_steps: int, starts: Sequence[int], k: int, eta: float
     return ts, torch.tensor(rows, dtype=torch.float32)
 
 
-def _from_starts_state(model, B: int, starts, k: int, device, eta: float) -> _LoopState:
+def starts_table_dpm(total_steps: int, starts: Sequence[int], k: int):
+    """:func:`starts_table` for DPM-Solver++(2M): rows ``{c0, c1, c2, c3, g, 0, 0, 0}``
+    (``schedule.dpm2m_row``; [len(ts), B, 8]).  A sample that has not started has
+    ``ETA_IDENT_ROW``; the step at which it starts has no history, so g = 0 there (DDIM), and
+    every later one takes the ``h`` of the sample's step before."""
+    ts, _ = starts_table(total_steps, starts, k)
+
+    def row(s, t):
+        if s < t:
+            return ETA_IDENT_ROW
+        return dpm2m_row(total_steps, t, k, None if s == t else dpm2m_step_h(total_steps, t + k, k))
+
+    return ts, torch.tensor([[row(s, t) for s in starts] for t in ts], dtype=torch.float32)
+
+
+def _from_starts_state(model, B: int, starts, k: int, device, eta: float, solver: str = "ddim") -> _LoopState:
     """Buffers + loop of :func:`ddim_from_starts`."""
     den = _Denoiser(model, device)
     T = model.total_steps
-    ts, coef = starts_table_eta(T, starts, k, eta) if eta > 0 else starts_table(T, starts, k)
+    dpm = solver == "dpmpp2m"
+    if dpm:
+        ts, coef = starts_table_dpm(T, starts, k)
+    else:
+        ts, coef = starts_table_eta(T, starts, k, eta) if eta > 0 else starts_table(T, starts, k)
     coef = coef.to(device)
     xs = torch.zeros(B, model.in_chans, *model.img_size, device=device)
     x0 = torch.zeros_like(xs)
     tt = _step_times(ts, B, device)
     nz = _StepNoise(model, B, device) if eta > 0 else None
-    s = _loop_state(model, B, device, den, xs, x0, eta=nz is not None)
-    step = _ddim_step(s, coef, True, nz)
+    s = _loop_state(model, B, device, den, xs, x0, eta=nz is not None, chain=not dpm)
+    step = _dpm_step(s, coef, True) if dpm else _ddim_step(s, coef, True, nz)
 
     def loop():
         s.begin(xs)
+        if dpm:
+            s.history(len(ts))
         for i in range(len(ts)):
             step(i, tt[i])
         s.write_back(x=xs, x0=x0)
@@ -681,7 +775,8 @@ def _from_starts_state(model, B: int, starts, k: int, device, eta: float) -> _Lo
 
 @torch.no_grad()
 def ddim_from_starts(model, x: torch.Tensor, starts: Sequence[int], k: int, device=None,
-                     use_graph: bool = True, eta: float = 0.0, noise_seed: Optional[int] = None) -> torch.Tensor:
+                     use_graph: bool = True, eta: float = 0.0, noise_seed: Optional[int] = None,
+                     solver: str = "ddim") -> torch.Tensor:
     """DDIM (jump ``k``) from per-sample start steps, all samples in ONE batch.
 
     Sample i joins the shared descending grid at its own ``starts[i]``; all starts
@@ -698,7 +793,13 @@ def ddim_from_starts(model, x: torch.Tensor, starts: Sequence[int], k: int, devi
     mode 6 (per-sample rows of 8 coefficients, the noise drawn in the epilogue); a sample
     that has not started is left exactly as it is.  ``noise_seed``: the run's noise seed
     (None: one draw from the global generator).
+
+    ``solver="dpmpp2m"`` (``eta`` = 0 only): DPM-Solver++(2M) steps as in :class:`DDIMSampler`,
+    with per-sample rows (:func:`starts_table_dpm`): one forward plus one
+    :func:`ops.dpm2m_rows_` launch per step; the step at which a sample joins is first-order.
+    Its loops are cached under their own kind of key, held to ``IMG2IMG_GRAPHS`` as well.
     """
+    _check_solver(solver, eta)
     device = torch.device(device) if device is not None else x.device
     T = model.total_steps
     B = x.shape[0]
@@ -708,7 +809,10 @@ def ddim_from_starts(model, x: torch.Tensor, starts: Sequence[int], k: int, devi
     key = ("img2img", B, tuple(starts), k, str(device))
     if eta > 0:
         key = ("img2img_eta", B, tuple(starts), k, str(device), eta)
-    st = _cached_loop(model, key, lambda: _from_starts_state(model, B, starts, k, device, eta), IMG2IMG_GRAPHS)
+    if solver == "dpmpp2m":
+        key = ("img2img_dpm", B, tuple(starts), k, str(device))
+    st = _cached_loop(model, key, lambda: _from_starts_state(model, B, starts, k, device, eta, solver),
+                      IMG2IMG_GRAPHS)
     st.x.copy_(x.to(device).float())
     if st.noise is not None:
         st.noise.set_seed(draw_noise_seed() if noise_seed is None else noise_seed)
@@ -719,7 +823,7 @@ def ddim_from_starts(model, x: torch.Tensor, starts: Sequence[int], k: int, devi
 @torch.no_grad()
 def img2img(model, draft: torch.Tensor, t_starts: Sequence[int] = tuple(range(1599, 2000, 50)), k: int = 10,
             device=None, generator: Optional[torch.Generator] = None, use_graph: bool = True,
-            eta: float = 0.0) -> torch.Tensor:
+            eta: float = 0.0, solver: str = "ddim") -> torch.Tensor:
     """Zero-shot draft->drawing (SDEdit-style) for several noise levels at once.
 
     For each t_start: x = sqrt(1-a) eps + sqrt(a) draft, a = 1 - sqrt(t_start/T)
@@ -731,7 +835,9 @@ def img2img(model, draft: torch.Tensor, t_starts: Sequence[int] = tuple(range(15
     step grid at its own start (the reference loops them one at a time at batch
     1); the loop is one cached hipGraph (:func:`ddim_from_starts`).  ``eta`` > 0: stochastic
     DDIM steps (what SDEdit uses), their noise seed one more draw from ``generator``.
+    ``solver="dpmpp2m"``: DPM-Solver++(2M) steps instead (``eta`` = 0 only; :func:`ddim_from_starts`).
     """
+    _check_solver(solver, eta)
     device = torch.device(device) if device is not None else next(model.parameters()).device
     T = model.total_steps
     starts = list(t_starts)
@@ -745,12 +851,12 @@ def img2img(model, draft: torch.Tensor, t_starts: Sequence[int] = tuple(range(15
     top = max(starts)
     if any((top - s) % k for s in starts):
         # different grids: run them one by one
-        return torch.cat([img2img(model, draft[i:i + 1], [s], k, device, generator, use_graph, eta)
+        return torch.cat([img2img(model, draft[i:i + 1], [s], k, device, generator, use_graph, eta, solver)
                           for i, s in enumerate(starts)])
     eps = torch.normal(0.0, 1.0, (B, C, H, W), generator=generator).to(device)
     x = img2img_noised(draft, eps, starts, T)
     seed = draw_noise_seed(generator) if float(eta) > 0 else None
-    x0 = ddim_from_starts(model, x, starts, k, device, use_graph, eta, seed)
+    x0 = ddim_from_starts(model, x, starts, k, device, use_graph, eta, seed, solver)
     return _unit_host(x0)
 
 
@@ -826,6 +932,9 @@ def inpaint(model, image: torch.Tensor, mask, k: int = 10, eta: float = 0.0, res
     it (``noise_seed=`` overrides it).  The loop is one hipGraph cached per (B, k, eta,
     resample), at most ``INPAINT_GRAPHS`` per model; image, mask, x_T and the seed are static
     buffers, so a new one of any of them is a replay.
+
+    The steps are first-order DDIM only: the paste rewrites ``x`` between forwards, which breaks
+    the x0-hat history a multistep solver (``DDIMSampler(solver="dpmpp2m")``) extrapolates from.
 
     Returns the final state -- at the last step x0-hat in the free region and ``image`` exactly
     in the kept one -- as host images in [0, 1] (``unit=False``: in [-1, 1])."""

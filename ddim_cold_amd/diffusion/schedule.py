@@ -96,6 +96,60 @@ def ddim_table_eta(total_steps: int, k: int, eta: float, start: int | None = Non
     return ts, coef
 
 
+def dpm2m_step_h(total_steps: int, t: int, k: int) -> float:
+    """The step ``h = lambda_{t-k} - lambda_t`` of one jump in half-log-SNR ``lambda = ln(alpha /
+    sigma)``, from the floats of :func:`ddim_coefficients`: ``ln(c2 / c3) - ln(c0 / c1)``;
+    ``inf`` for the last jump onto a_{t-k} = 1 (``c3`` = 0)."""
+    c0, c1, c2, c3 = ddim_coefficients(total_steps, t, k)
+    if c3 == 0.0:
+        return math.inf
+    return math.log(c2 / c3) - math.log(c0 / c1)
+
+
+def dpm2m_row(total_steps: int, t: int, k: int, h_prev):
+    """The 8-float coefficient row ``{c0, c1, c2, c3, g, 0, 0, 0}`` of one DPM-Solver++(2M) jump
+    t -> t-k (Lu et al. 2022, Algorithm 2) of an x0-predicting model; the update it describes is
+
+        ``x_next = c2 x0 + c3 (x_t - c0 x0) / c1 + g (x0 - x0_prev)``     (``ops.dpm2m_rows_``)
+
+    with ``c0..c3`` the very floats of :func:`ddim_coefficients`, ``x0`` this step's clamped
+    prediction and ``x0_prev`` the previous step's.
+
+    Derivation.  With alpha = sqrt(a), sigma = sqrt(1 - a), lambda = ln(alpha / sigma) and
+    ``h = lambda_{t-k} - lambda_t`` the multistep solver steps
+
+        ``x_next = (sigma_next / sigma_t) x_t - alpha_next (e^{-h} - 1) D``,
+        ``D = (1 + 1 / (2 r)) x0 - (1 / (2 r)) x0_prev``,   ``r = h_prev / h``.
+
+    ``e^{-h} = (sigma_next / alpha_next) (alpha_t / sigma_t) = c3 c0 / (c2 c1)``, so ``-alpha_next
+    (e^{-h} - 1) = c2 - c3 c0 / c1``, and with D = x0 the step is ``(c3 / c1) x_t + (c2 - c3 c0 /
+    c1) x0 = c2 x0 + c3 (x_t - c0 x0) / c1``: DDIM, the solver's first-order member.  The rest of
+    D contributes ``(c2 - c3 c0 / c1) (1 / (2 r)) (x0 - x0_prev)``, hence
+
+        ``g = (c2 - c3 c0 / c1) h / (2 h_prev)``,   ``h = ln(c2 / c3) - ln(c0 / c1)``.
+
+    ``g`` is exactly 0.0, and the step DDIM's, when ``h_prev`` is None (a sample's first step:
+    no history) and when ``c3 == 0`` (the last jump onto a = 1: h is infinite, the solver's
+    final step is first-order).  Computed in Python floats, stored as fp32 by the tables."""
+    c0, c1, c2, c3 = ddim_coefficients(total_steps, t, k)
+    g = 0.0
+    if h_prev is not None and c3 != 0.0:
+        h = math.log(c2 / c3) - math.log(c0 / c1)
+        g = (c2 - c3 * c0 / c1) * h / (2.0 * h_prev)
+    return c0, c1, c2, c3, g, 0.0, 0.0, 0.0
+
+
+def dpm2m_table(total_steps: int, k: int, start: int | None = None, device="cpu"):
+    """``(ts, [steps, 8] fp32 rows of :func:`dpm2m_row`)`` over :func:`ddim_timesteps`: the first
+    row has no history (g = 0), every later one the ``h`` of the row before it."""
+    ts = ddim_timesteps(total_steps, k, start)
+    rows, h_prev = [], None
+    for t in ts:
+        rows.append(dpm2m_row(total_steps, t, k, h_prev))
+        h_prev = dpm2m_step_h(total_steps, t, k)
+    return ts, torch.tensor(rows, dtype=torch.float32, device=device)
+
+
 def repaint_row(total_steps: int, t: int, k: int, jump: bool):
     """``(ka, kb, ra, rb)`` of the inpainting mask step after the DDIM jump t -> t-k
     (``ops.repaint_rows_``; Lugmayr et al. 2022).  The known region is pasted at the level the

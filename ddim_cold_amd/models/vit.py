@@ -333,12 +333,13 @@ class DiffusionVisionTransformer(nn.Module):
 
     # ------------------------------------------------------------------ samplers
     @torch.no_grad()
-    def sampler(self, device, k=10, N=128, generator=None, use_graph=True, verbose=False, eta=0.0):
+    def sampler(self, device, k=10, N=128, generator=None, use_graph=True, verbose=False, eta=0.0, solver="ddim"):
         """DDIM k-step sampler (`ViT.py:220-237`); returns CPU images in [0, 1].  ``eta`` in
-        [0, 1]: the DDIM family's noise scale (0: deterministic, 1: DDPM ancestral sampling)."""
+        [0, 1]: the DDIM family's noise scale (0: deterministic, 1: DDPM ancestral sampling).
+        ``solver="dpmpp2m"``: DPM-Solver++(2M) steps on the same grid (``eta`` = 0 only)."""
         from ..diffusion.samplers import DDIMSampler
-        return DDIMSampler(self, device, k=k, use_graph=use_graph, eta=eta).sample(N, generator=generator,
-                                                                                     verbose=verbose)
+        return DDIMSampler(self, device, k=k, use_graph=use_graph, eta=eta, solver=solver).sample(
+            N, generator=generator, verbose=verbose)
 
     def inpaint(self, image, mask, k=10, eta=0.0, resample=1, device=None, generator=None, use_graph=True, **kw):
         """Keep ``image`` where ``mask`` is 1 and generate the rest
@@ -348,11 +349,11 @@ class DiffusionVisionTransformer(nn.Module):
                        use_graph=use_graph, **kw)
 
     @torch.no_grad()
-    def diffusion_sequence(self, device, k=100, N=5, generator=None, eta=0.0):
+    def diffusion_sequence(self, device, k=100, N=5, generator=None, eta=0.0, solver="ddim"):
         """DDIM trajectory recorder (`ViT.py:239-256`): [x_T, x0_hat_1, ...] on CPU (``eta``
-        as in :meth:`sampler`)."""
+        and ``solver`` as in :meth:`sampler`)."""
         from ..diffusion.samplers import DDIMSampler
-        return DDIMSampler(self, device, k=k, use_graph=False, eta=eta).sequence(N, generator=generator)
+        return DDIMSampler(self, device, k=k, use_graph=False, eta=eta, solver=solver).sequence(N, generator=generator)
 
     @torch.no_grad()
     def cold_sampler(self, device, k=10, N=49, generator=None, use_graph=True, predict="prev", algorithm=2):

@@ -24,7 +24,7 @@ __all__ = [
     "sqnorm", "adamw_step", "weight_ema_decay", "advance_counters", "ddim_step", "ddim_step_", "randn_", "q_sample",
     "pixelate_pair", "cold_batch", "gauss_batch", "batch_draw", "BatchSource", "head_step_rows_", "cold_step_", "cold_step_rows_",
     "image_to_rows", "rows_to_image", "embed_weight_rows", "patch_embed_cold_fwd", "ln_fold_", "SITE_STEP_NOISE",
-    "repaint_rows_", "SITE_PASTE_NOISE", "SITE_JUMP_NOISE", "SITE_LOOP_FORWARDS",
+    "repaint_rows_", "dpm2m_rows_", "SITE_PASTE_NOISE", "SITE_JUMP_NOISE", "SITE_LOOP_FORWARDS",
     "HEAD_DDIM", "HEAD_CLAMP", "HEAD_DDIM_EACH", "HEAD_ETA", "HEAD_ETA_EACH",
 ]
 
@@ -867,6 +867,22 @@ def repaint_rows_(x, known, mask, coef, rng, site_paste: int, site_jump: int, pa
     x.copy_(out)
     if patches_out is not None:
         patches_out[wrote] = out.to(torch.bfloat16)[wrote]
+
+
+def dpm2m_rows_(x, x0, x0_prev, coef, batch: int, each: bool = False, patches_out=None):
+    """DPM-Solver++(2M) step, in place on the sampler's fp32 patch rows ``x`` [B*P, F]
+    (:func:`reference.dpm2m_rows`): ``x <- c2 x0 + c3 (x - c0 x0) / c1 + g (x0 - x0_prev)`` with
+    ``x0`` the clamped prediction of this step's forward and ``x0_prev`` the previous step's
+    (distinct buffers of ``x``'s shape).  ``coef``: device fp32 rows ``{c0, c1, c2, c3, g, 0, 0,
+    0}`` (``schedule.dpm2m_row``), one, or with ``each`` one per sample [batch, 8].  A row with
+    ``g == 0`` is the DDIM step and does not read ``x0_prev``.  ``patches_out`` (bf16, same
+    shape): the bf16 of the new ``x``, the next step's patch rows."""
+    if _hip(x):
+        return _ops().dpm2m_rows_(x, x0, x0_prev, coef, int(batch), bool(each), patches_out)
+    out = ref.dpm2m_rows(x, x0, x0_prev, coef, int(batch), bool(each))
+    x.copy_(out)
+    if patches_out is not None:
+        patches_out.copy_(out.to(torch.bfloat16))
 
 
 def randn_(out, rng, site: int):

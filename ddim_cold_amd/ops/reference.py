@@ -500,6 +500,34 @@ def repaint_rows(x, known, mask, coef, rng, site_paste: int, site_jump: int):
     return _fma32(rb, z2, ra * y), torch.ones_like(keep)
 
 
+def dpm2m_rows(x, x0, x0_prev, coef, batch: int, each: bool):
+    """DPM-Solver++(2M) step (``schedule.dpm2m_row``) on the fp32 patch-row state ``x`` [B*P, F],
+    the arithmetic of ``dpm2m_rows_kernel`` with its roundings:
+
+        ``de  = fl(c3 * (fma(-c0, x0, x) / c1))``
+        ``det = fma(c2, x0, de)``
+        ``out = (g == 0) ? det : fma(g, fl(x0 - x0_prev), det)``
+
+    ``x0`` the clamped prediction, ``x0_prev`` the previous step's; ``coef`` fp32 rows ``{c0, c1,
+    c2, c3, g, 0, 0, 0}``: one, or (``each``) one per sample [batch, 8], a sample being
+    ``numel / batch`` consecutive elements.  Where ``g == 0`` nothing of ``x0_prev`` reaches the
+    result (the kernel does not load it).  Returns the new ``x``."""
+    batch = int(batch)
+    if batch < 1 or x.numel() % (4 * batch):
+        raise ValueError("dpm2m_rows: the element count must be a multiple of 4 * batch")
+    if x0.shape != x.shape or x0_prev.shape != x.shape:
+        raise ValueError("dpm2m_rows: x, x0 and x0_prev of one shape")
+    if coef.numel() != (8 * batch if each else 8):
+        raise ValueError("dpm2m_rows: coef must hold one row of 8 floats, or (each) one per sample")
+    cf = coef.detach().float().to(x.device).reshape(-1, 8)
+    xs, p, pp = (v.reshape(cf.shape[0], -1) for v in (x, x0, x0_prev))
+    c0, c1, c2, c3, g = (cf[:, i:i + 1] for i in range(5))
+    de = c3 * (_fma32(-c0, p, xs) / c1)
+    det = _fma32(c2, p, de)
+    out = torch.where(g == 0, det, _fma32(g, p - pp, det))
+    return out.reshape(x.shape)
+
+
 def pixelate(img, factor: int):
     """NEAREST down to floor(W/f) then NEAREST up (`diffusion_loader.py:79-83`)."""
     H, W = img.shape[-2:]
